@@ -18,6 +18,11 @@ src/read_alignment_scanner.rs:508), the windows are dealt to the ranks balanced 
 gathered to rank 0 over RCCL (peer -> root send/recv, the path's only exchange step).  After the timed region rank 0 checks
 that the gathered records equal its own single-GPU result of the whole read set, bit for bit.  `--scaling weak` gives every
 rank its own read set of the full size instead.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the line can carry
+(counting-kernel statistics and the roofline object, `overlap`, `window_50k`, `end_to_end` / `pcie_inclusive`, the CPU baseline and
+its parity sample; N > 1: `gather_modes.c_abi`, `verify`, `end_to_end_sharded`).  `--dump-outputs DIR` writes a fixed, seeded sample
+of the last timed step's result records as DIR/<name>.npy (float64), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -527,29 +532,38 @@ def stream_main(args, cfg, dev, dev_index, chunk_reads):
         if int(tm.heavy_kernel):
             agg["heavy_kernel"] = int(tm.heavy_kernel)
 
-    # algorithmic bytes: one pass of the counting kernels outside the timed region (the production light-item kernel carries no counters)
-    cnt_run = stream.StreamRunner(index, dev, 1)
-    for e_ in cnt_run.engines:
-        e_.set_stats()
+    if args.full:
+        # algorithmic bytes: one pass of the counting kernels outside the timed region (the production light-item kernel carries no counters)
+        cnt_run = stream.StreamRunner(index, dev, 1)
+        for e_ in cnt_run.engines:
+            e_.set_stats()
 
-    def record_algo(tm):
-        agg["algo"] += int(tm.algo_bytes)
+        def record_algo(tm):
+            agg["algo"] += int(tm.algo_bytes)
 
-    cnt_run.run(descs, record=record_algo)
-    cnt_run.sync()
-    for e_ in cnt_run.engines:
-        e_.close()
+        cnt_run.run(descs, record=record_algo)
+        cnt_run.sync()
+        for e_ in cnt_run.engines:
+            e_.close()
     one = stream.StreamRunner(index, dev, 1)
     for _ in range(max(1, args.warmup)):
         one.run(descs)
     one.sync()
+    parts = [None] * len(descs)
+
+    def keep_sample(k, eng_, out_):  # (--dump-outputs, last step only: a batch's result lives until the next batch's call)
+        eng_.sync()
+        parts[k] = output_sample(out_, dev, DUMP_ITEMS // len(descs), DUMP_OPS // len(descs))
+
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one.run(descs, record=record)
+    for i in range(args.steps):
+        one.run(descs, record=record, consume=keep_sample if (args.dump_outputs and i == args.steps - 1) else None)
     one.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, parts)
     n_calls = args.steps * len(descs)
     kms = {"k_lift_lanes": float(np.sum(times["lanes"])) / n_calls, "k_lift_mid": float(np.sum(times["mid"])) / n_calls,
            "k_lift_tiles": float(np.sum(times["lift"])) / n_calls, "k_lift_big": float(np.sum(times["big"])) / n_calls,
@@ -572,14 +586,15 @@ def stream_main(args, cfg, dev, dev_index, chunk_reads):
                    "lane_items_per_gpu": agg["lane_items"] // args.steps, "retry_items_per_gpu": agg["retry_items"] // args.steps, "seq_fmt": "bam4",
                    "parallelism": "one read set on one set of contigs, lifted as consecutive batches through one context (one step = one pass over all batches)",
                    "host_workers_per_gpu": 1, "kernel_source_hash": plo_build.source_hash(), "gather": "none"},
-        "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "frac_of_copy_ceiling": achieved / HBM_COPY_CEILING_GBS, "traffic": None, "algorithmic_bytes_per_launch": int(algo_per_call * share),
-                     "kernel_ms": dom_ms, "launches_per_step": len(descs), "enumerate_ms": float(np.sum(times["enum"])) / n_calls,
-                     "lift_lanes_ms": kms["k_lift_lanes"], "lift_tiles_ms": kms["k_lift_tiles"], "lift_big_ms": kms["k_lift_big"],
-                     "lift_mid_ms": kms["k_lift_mid"], "lift_retry_ms": kms["k_lift_retry"], "lift_heavy_ms": kms["k_lift_lanes_g"], "heavy_kernel": heavy_name if agg.get("heavy_kernel", 0) else None},
     }
+    if args.full:
+        result["roofline"] = {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                              "frac_of_copy_ceiling": achieved / HBM_COPY_CEILING_GBS, "traffic": None, "algorithmic_bytes_per_launch": int(algo_per_call * share),
+                              "kernel_ms": dom_ms, "launches_per_step": len(descs), "enumerate_ms": float(np.sum(times["enum"])) / n_calls,
+                              "lift_lanes_ms": kms["k_lift_lanes"], "lift_tiles_ms": kms["k_lift_tiles"], "lift_big_ms": kms["k_lift_big"],
+                              "lift_mid_ms": kms["k_lift_mid"], "lift_retry_ms": kms["k_lift_retry"], "lift_heavy_ms": kms["k_lift_lanes_g"], "heavy_kernel": heavy_name if agg.get("heavy_kernel", 0) else None}
     one.close()
-    if args.overlap_workers > 1:
+    if args.full and args.overlap_workers > 1:
         two = stream.StreamRunner(index, dev, args.overlap_workers)
         two.run(descs)
         two.sync()
@@ -594,7 +609,7 @@ def stream_main(args, cfg, dev, dev_index, chunk_reads):
                              "ms_per_step": odt / args.steps * 1e3,
                              "note": "the same passes with the batches dealt to several host workers (one context + HIP stream each)"}
         two.close()
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # parity on every batch's strided sample + the CPU baseline on the first batch
         try:
             chk = api.Engine(index)
@@ -692,6 +707,48 @@ def finalize(result) -> int:
     return 0
 
 
+DUMP_ITEMS = 65536  # sampled items of a dump (shared by the batches of a streamed pass)
+DUMP_OPS = 4 << 20  # at most this many of the sampled items' output CIGAR ops (8 B each as float64: 32 MB)
+DUMP_SEED = 20251016
+
+
+def output_sample(out, dev, max_items: int = DUMP_ITEMS, max_ops: int = DUMP_OPS, seed: int = DUMP_SEED) -> dict:
+    """A fixed, seeded sample of one call's result records (plo_batch_out, still in the engine's buffers; the caller has synchronised),
+    in a layout-independent form: the items in (read segment, contig segment) order -- the order of the result arrays depends on the
+    routing -- then `max_items` of them picked by a seeded generator, their fields and their output CIGAR ops (concatenated, cut at
+    `max_ops`).  Every value is an integer that float64 holds exactly."""
+    t = plo_gather.tensors_from_out(out, dev)
+    u32 = 0xFFFFFFFF
+    seg = t["item_seg"].to(torch.int64) & u32
+    cseg = t["item_cseg"].to(torch.int64) & u32
+    n = int(seg.numel())
+    order = torch.argsort((seg << 32) | cseg, stable=True)
+    pick = np.sort(np.random.default_rng(seed).choice(n, size=min(n, max_items), replace=False)) if n else np.zeros(0, np.int64)
+    idx = order[torch.from_numpy(pick.astype(np.int64)).to(dev)]
+    lens = t["item_cigar_len"].to(torch.int64)[idx] & u32
+    keep = int(torch.searchsorted(torch.cumsum(lens, 0), torch.tensor([max_ops], device=dev), right=True).item()) if n else 0
+    idx, lens = idx[:keep], lens[:keep]
+    offs = t["item_cigar_off"][idx]
+    starts = torch.cumsum(lens, 0) - lens
+    total = int(lens.sum().item()) if keep else 0
+    pos = torch.repeat_interleave(offs - starts, lens) + torch.arange(total, device=dev, dtype=torch.int64)
+    res = {name: ((t[name].to(torch.int64)[idx] & u32) if tdt == torch.int32 else t[name][idx].to(torch.int64)).to(torch.float64).cpu().numpy()
+           for name, _, tdt in plo_gather.ITEM_FIELDS if name != "item_cigar_off"}
+    res["cigar"] = ((t["cigar"].to(torch.int64)[pos] & u32) if total else torch.zeros(0, dtype=torch.int64)).to(torch.float64).cpu().numpy()
+    res["counts"] = np.array([n, int((t["item_cigar_len"].to(torch.int64) & u32).sum().item()) if n else 0], dtype=np.float64)
+    return res
+
+
+def dump_outputs(dirname: str, parts) -> None:
+    """writes the samples of output_sample() (one per batch of the step) as dirname/<field>.npy, the batches' samples concatenated;
+    counts.npy holds (items, output CIGAR ops) of every batch"""
+    os.makedirs(dirname, exist_ok=True)
+    for name in parts[0]:
+        arr = np.stack([p[name] for p in parts]) if name == "counts" else np.concatenate([p[name] for p in parts])
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    log(f"[bench] outputs of the last step: {sum(int(p['item_seg'].size) for p in parts)} sampled items -> {dirname}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -702,7 +759,7 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default=os.environ.get("PLO_BENCH_SCALING", "strong"),
                     help="N > 1: strong = one read set sharded by windows over the ranks (BASELINE configs[3]); weak = every rank "
                          "its own read set of the full size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the verification of the BAM runs")
     ap.add_argument("--window-calls", type=int, default=200,
                     help="N = 1: calls of the supplementary `window_50k` measurement (0 = skip: traced / counter runs skip it, its launches "
                          "would enter the per-kernel averages)")
@@ -734,6 +791,13 @@ def main():
                     help="N > 1: nccl = RCCL over xGMI (device tensors, the production path); gloo = the same shard -> lift -> gather -> "
                          "verify run with the rank payloads passing through host tensors -- for boxes with ONE GPU, where RCCL refuses two "
                          "ranks on a device (PLO_BENCH_SHARE_GPU=1 lets the ranks share it)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the counting-kernel statistics and the roofline object, `overlap`, `window_50k`, "
+                         "`end_to_end` / `pcie_inclusive`, the CPU baseline with its parity sample; N > 1: `gather_modes.c_abi`, `verify`, "
+                         "`end_to_end_sharded`.  Without it a run sets up, warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed, seeded sample of the last step's result records as DIR/<name>.npy (float64, "
+                         "items in (read segment, contig segment) order; see dump_outputs()).  N > 1: rank 0's own share")
     args = ap.parse_args()
 
     # N > 1 without a launcher: start the N ranks ourselves (before anything touches the GPU), relay rank 0's line and the exit code
@@ -816,12 +880,15 @@ def main():
     # The statistics of the batch -- algorithmic bytes (SURVEY.md 8(d)'s B_item, counted per item on the device) and lane utilisation -- come
     # from ONE call on a context of its own that asks for the counting instantiation of the light-item kernel (plo_ctx_set_stats); the
     # timed steps below run the production kernel, which is compiled without the counters (VERDICT r5, next #1a).
-    eng_stats = api.Engine(index, stream=streams[0].cuda_stream).set_stats()
-    eng_stats.liftover_batch_dev(desc)
-    stats_tm = eng_stats.timing()
-    stats = {"algo_bytes": int(stats_tm.algo_bytes), "lane_utilisation": float(stats_tm.lane_utilisation), "lanes_ms_counting_kernel": float(stats_tm.lanes_ms)}
-    eng_stats.close()
-    torch.cuda.synchronize()
+    # (--full only: they feed the roofline object)
+    stats = None
+    if args.full:
+        eng_stats = api.Engine(index, stream=streams[0].cuda_stream).set_stats()
+        eng_stats.liftover_batch_dev(desc)
+        stats_tm = eng_stats.timing()
+        stats = {"algo_bytes": int(stats_tm.algo_bytes), "lane_utilisation": float(stats_tm.lane_utilisation), "lanes_ms_counting_kernel": float(stats_tm.lanes_ms)}
+        eng_stats.close()
+        torch.cuda.synchronize()
 
     def barrier():
         if dist is not None:
@@ -898,6 +965,37 @@ def main():
 
     def make_result(dt_, gather_desc):
         tm = eng.timing()
+        result = {
+            "metric": "lifted HiFi reads/sec (whole node)",
+            "value": total_reads * args.steps / dt_,
+            "unit": "reads/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt_ / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "int32",
+            "dtype_note": "the reference computes in i64 / usize; every batch is range-checked on the device (PLO_ERR_RANGE beyond the 31-bit BAM domain), inside the domain 32-bit results are bit-identical",
+            "data": "synthetic",
+            "config": {"workload": cfg.name, "reads_total": int(total_reads), "reads_this_rank": my_reads, "read_len_mean": cfg.read_len_mean,
+                       "items_per_gpu": int(tm.n_items), "in_ops_per_gpu": int(tm.n_in_ops), "out_ops_per_gpu": int(tm.n_out_ops),
+                       "large_items_per_gpu": int(tm.n_big_items), "mid_items_per_gpu": int(tm.n_mid_items),
+                       "retry_items_per_gpu": int(tm.n_retry_items), "lane_items_per_gpu": int(tm.n_lane_items), "heavy_lane_items_per_gpu": int(tm.n_heavy_lane_items), "seq_fmt": "bam4",
+                       "tile_geometry": {"slice_elements": int(tm.tile_cap), "window": int(tm.tile_window)},
+                       "parallelism": (f"one read set, 20 Mb windows dealt to {world} ranks by input ops" if strong else f"{world} independent read sets"),
+                       "host_workers_per_gpu": n_workers, "kernel_source_hash": plo_build.source_hash(),
+                       "gather": gather_desc, "dist_backend": (args.dist_backend if dist is not None else None),
+                       "launched_by": ("bench.py (child torch.distributed.run)" if os.environ.get("PLO_BENCH_LAUNCHED") else
+                                       ("external launcher" if world > 1 else "single process"))},
+        }
+        if args.full:
+            result["roofline"] = roofline(tm)
+        return result
+
+    def roofline(tm):
+        """the roofline object (--full): the kernels' HIP-event times of the timed steps against the counting call's algorithmic bytes"""
         # the heavy items' kernel under its own name (plo_timing::heavy_kernel says which one `heavy_lanes_ms` is the time of)
         heavy_name = {2: "k_lift_lanes_g_w3", 3: "k_lift_stream"}.get(int(tm.heavy_kernel), "k_lift_lanes_g")
         kms = {"k_lift_lanes": float(np.mean(times["lanes"])), "k_lift_mid": float(np.mean(times["mid"])), "k_lift_tiles": float(np.mean(times["lift"])),
@@ -954,41 +1052,21 @@ def main():
         if traffic and dom_ms > 0:
             traffic_obj = {"traffic_GBps": traffic / (dom_ms * 1e-3) / 1e9, "traffic_frac_of_peak": traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                            "traffic_over_algorithmic": traffic / max(1.0, algo_bytes * share)}
-        result = {
-            "metric": "lifted HiFi reads/sec (whole node)",
-            "value": total_reads * args.steps / dt_,
-            "unit": "reads/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt_ / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "dtype_note": "the reference computes in i64 / usize; every batch is range-checked on the device (PLO_ERR_RANGE beyond the 31-bit BAM domain), inside the domain 32-bit results are bit-identical",
-            "data": "synthetic",
-            "config": {"workload": cfg.name, "reads_total": int(total_reads), "reads_this_rank": my_reads, "read_len_mean": cfg.read_len_mean,
-                       "items_per_gpu": int(tm.n_items), "in_ops_per_gpu": int(tm.n_in_ops), "out_ops_per_gpu": int(tm.n_out_ops),
-                       "large_items_per_gpu": int(tm.n_big_items), "mid_items_per_gpu": int(tm.n_mid_items),
-                       "retry_items_per_gpu": int(tm.n_retry_items), "lane_items_per_gpu": int(tm.n_lane_items), "heavy_lane_items_per_gpu": int(tm.n_heavy_lane_items), "seq_fmt": "bam4",
-                       "tile_geometry": {"slice_elements": int(tm.tile_cap), "window": int(tm.tile_window)},
-                       "parallelism": (f"one read set, 20 Mb windows dealt to {world} ranks by input ops" if strong else f"{world} independent read sets"),
-                       "host_workers_per_gpu": n_workers, "kernel_source_hash": src_hash,
-                       "gather": gather_desc, "dist_backend": (args.dist_backend if dist is not None else None),
-                       "launched_by": ("bench.py (child torch.distributed.run)" if os.environ.get("PLO_BENCH_LAUNCHED") else
-                                       ("external launcher" if world > 1 else "single process"))},
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "frac_of_copy_ceiling": achieved / HBM_COPY_CEILING_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": int(algo_bytes * share), "kernel_ms": dom_ms,
-                         "enumerate_ms": float(np.mean(times["enum"])), "enumerate_pass": enum_obj, "lift_lanes_ms": kms["k_lift_lanes"], "lift_tiles_ms": kms["k_lift_tiles"],
-                         "lift_big_ms": kms["k_lift_big"], "lift_mid_ms": kms["k_lift_mid"], "lift_retry_ms": kms["k_lift_retry"], "lift_heavy_ms": kms[heavy_name], "heavy_kernel": heavy_name if int(tm.heavy_kernel) else None,
-                         "lane_utilisation": stats["lane_utilisation"],  # lanes at work / (64 x trips) of the lane kernels' liftover loop and shift rounds
-                         "statistics_from": "one call of the counting kernel outside the timed region (plo_ctx_set_stats); the timed kernel carries no counters",
-                         "lanes_ms_counting_kernel": stats["lanes_ms_counting_kernel"],
-                         "host_syncs_per_call": int(tm.host_syncs), **issue_obj, **traffic_obj},
-        }
-        return result
+        return {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "frac_of_copy_ceiling": achieved / HBM_COPY_CEILING_GBS, "traffic": traffic,
+                "algorithmic_bytes_per_launch": int(algo_bytes * share), "kernel_ms": dom_ms,
+                "enumerate_ms": float(np.mean(times["enum"])), "enumerate_pass": enum_obj, "lift_lanes_ms": kms["k_lift_lanes"], "lift_tiles_ms": kms["k_lift_tiles"],
+                "lift_big_ms": kms["k_lift_big"], "lift_mid_ms": kms["k_lift_mid"], "lift_retry_ms": kms["k_lift_retry"], "lift_heavy_ms": kms[heavy_name], "heavy_kernel": heavy_name if int(tm.heavy_kernel) else None,
+                "lane_utilisation": stats["lane_utilisation"],  # lanes at work / (64 x trips) of the lane kernels' liftover loop and shift rounds
+                "statistics_from": "one call of the counting kernel outside the timed region (plo_ctx_set_stats); the timed kernel carries no counters",
+                "lanes_ms_counting_kernel": stats["lanes_ms_counting_kernel"],
+                "host_syncs_per_call": int(tm.host_syncs), **issue_obj, **traffic_obj}
+
+    def dump_last_step():
+        """--dump-outputs: the sample of the last timed step's result, still in the buffers of the context that computed it"""
+        k = (args.steps - 1) % n_workers
+        engs[k].sync()
+        dump_outputs(args.dump_outputs, [output_sample(last_out[k], dev)])
 
     dt_ng = None
     gather_modes = None
@@ -997,6 +1075,8 @@ def main():
         dt = timed(lambda n: run_steps(n, True), args.steps)
         total_reads = float(my_reads)
         result = make_result(dt, "none")
+        if args.dump_outputs:
+            dump_last_step()
     else:
         nr = torch.tensor([my_reads], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(nr, op=dist.ReduceOp.SUM)
@@ -1060,6 +1140,8 @@ def main():
             return timed(lambda n: run_steps(n, False), args.steps)
 
         dt_sync = guarded(sync_run)
+        if dt_sync is not None and args.dump_outputs and rank == 0:
+            dump_last_step()
         result = fallback
         if dt_sync is None:
             if rank == 0:
@@ -1113,7 +1195,7 @@ def main():
         # (on by default with one rank -- what the one-GPU boxes of this pool can run, RCCL refuses two ranks on one device -- and with
         # PLO_BENCH_ABI_GATHER=1: a multi-rank exchange through it has not run on hardware yet, and a collective that hangs would take the
         # complete measurements above with it)
-        abi_on = os.environ.get("PLO_BENCH_ABI_GATHER", "1" if world == 1 else "0") == "1"
+        abi_on = args.full and os.environ.get("PLO_BENCH_ABI_GATHER", "1" if world == 1 else "0") == "1"
         if dt_sync is not None and not host_comm and n_workers == 1 and abi_on:
             def abi_run():
                 ag = plo_gather.AbiGather(index.lib, dist, rank, world, dev_index)
@@ -1223,7 +1305,7 @@ def main():
                                      "batches per step on two contexts, the exchange of batch i under the compute of batch i+1")
 
     overlap = None
-    if dist is None and n_workers == 1 and args.overlap_workers > 1:
+    if args.full and dist is None and n_workers == 1 and args.overlap_workers > 1:
         # supplementary: the same K batches dealt to several workers (not `value`: see --workers)
         ow = args.overlap_workers
         o_streams = [torch.cuda.Stream(device=dev) for _ in range(ow)]
@@ -1251,7 +1333,7 @@ def main():
     # a reference-sized window (the reference lifts ~50 k reads per 20 Mb window task, src/read_alignment_scanner.rs:508-534,575): the
     # per-call fixed cost -- launches, host round trips -- against a batch forty times smaller than the headline's
     window_50k = None
-    if dist is None and n_workers == 1 and w.n_reads >= 100_000 and args.window_calls > 0:
+    if args.full and dist is None and n_workers == 1 and w.n_reads >= 100_000 and args.window_calls > 0:
         try:
             lo = w.n_reads // 2
             wdb = devbatch.DeviceBatch.from_workload(w, lo, lo + 50_000)
@@ -1312,9 +1394,10 @@ def main():
             no_gather = {"value": total_reads * args.steps / dt_ng, "unit": "reads/s", "ms_per_step": dt_ng / args.steps * 1e3,
                          "note": "same K steps without the record gather (each rank keeps / writes its own shard)"}
             # one more synchronous step whose gathered records rank 0 compares with its own result of the WHOLE read set
-            step(0)
-            torch.cuda.synchronize()
-            if strong and not args.no_verify:
+            if args.full:
+                step(0)
+                torch.cuda.synchronize()
+            if args.full and strong and not args.no_verify:
                 if rank == 0:
                     seg_maps = [plo_gather.local_to_global_segments(w, shard.rank_read_ranges(wins, deal, r)).to(comm_dev) for r in range(world)]
                     got_all = plo_gather.combine(last_gather[0], seg_maps)
@@ -1351,7 +1434,7 @@ def main():
                 barrier()
 
         # BASELINE configs[3] as a BAM run: one input BAM, every rank its part of it (plo_bam_open_range), its own output shard
-        if dist is not None and strong and args.e2e_reads > 0:
+        if args.full and dist is not None and strong and args.e2e_reads > 0:
             e2e_sh = end_to_end_sharded(w, index, args.e2e_reads, args.e2e_window, args.e2e_workers, dist, rank, world, verify=not args.no_cpu_baseline)
     except Exception as e:  # noqa: BLE001 -- supplementary objects must never hide the measurement
         log(f"[bench] supplementary distributed measurements failed: {e!r}")
@@ -1362,7 +1445,7 @@ def main():
         if obj is not None:
             result[name] = obj
     ixd_host = None
-    if rank == 0 and world == 1 and dist is None and args.e2e_reads > 0:
+    if args.full and rank == 0 and world == 1 and dist is None and args.e2e_reads > 0:
         try:
             ixd_host = w.index_data()
             e2e, pcie = end_to_end(w, index, ixd_host, args.e2e_reads, args.e2e_window, args.e2e_workers, int(os.environ.get("PLO_BENCH_IO_THREADS", "0")) or max(2, min(64, pipeline_cpus())),
@@ -1373,7 +1456,7 @@ def main():
         except Exception as e:  # supplementary objects must never hide the measurement
             log(f"[bench] end_to_end failed: {e!r}")
             result["end_to_end"] = None
-    if rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
         try:
             got = devbatch.download(eng, last_out[0])
             cb, ok, n_checked = cpu_baseline(w, got, ixd=ixd_host)

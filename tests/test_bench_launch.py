@@ -51,7 +51,7 @@ def test_bench_starts_two_ranks_by_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PLO_BENCH_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", "chr20", "--reads", "30000",
-                        "--steps", "3", "--warmup", "1", "--e2e-reads", "4000", "--e2e-window", "700"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--steps", "3", "--warmup", "1", "--full", "--e2e-reads", "4000", "--e2e-window", "700"], env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout  # ONE JSON line
@@ -75,7 +75,7 @@ def test_bench_two_ranks_lift_wgs30x_as_a_window_pipeline():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PLO_BENCH_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", "wgs30x", "--steps", "2", "--warmup", "1",
-                        "--e2e-reads", "0", "--pipeline-batches", "4", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=2400)
+                        "--full", "--e2e-reads", "0", "--pipeline-batches", "4", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=2400)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
     assert r["n_gpus"] == 2 and r["config"]["workload"] == "wgs30x" and r["config"]["reads_total"] == 2_000_000 and r["value"] > 0

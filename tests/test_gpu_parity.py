@@ -542,7 +542,7 @@ def test_rccl_gather_path_with_one_rank():
     env = dict(os.environ, PLO_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                PLO_BENCH_GATHER_TIMEOUT="120")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "chr20", "--reads", "30000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--e2e-reads", "0", "--overlap-workers", "0"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--e2e-reads", "0", "--overlap-workers", "0"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, (p.stdout[-1500:], p.stderr[-1500:])

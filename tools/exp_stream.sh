@@ -8,7 +8,7 @@ run() {  # label, env..., -- bench args
   envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout 900 python bench.py --workload stress --no-cpu-baseline --e2e-reads 0 --window-calls 0 "$@" > /tmp/exp.json 2> /tmp/exp.err
+  env "${envs[@]}" timeout 900 python bench.py --full --workload stress --no-cpu-baseline --e2e-reads 0 --window-calls 0 "$@" > /tmp/exp.json 2> /tmp/exp.err
   python3 - "$label" <<'PY' >> gpurun_out/exp_stream.txt
 import json, sys
 try:
