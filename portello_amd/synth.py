@@ -25,6 +25,7 @@ _ACGT = torch.tensor([65, 67, 71, 84], dtype=torch.uint8)  # A C G T
 _ASCII_TO_BAM4 = torch.full((256,), 15, dtype=torch.uint8)
 for _i, _c in enumerate("=ACMGRSVTWYHKDBN"):
     _ASCII_TO_BAM4[ord(_c)] = _i
+_IUPAC2 = torch.tensor(list(b"MRWSYKVHDB"), dtype=torch.uint8)  # the ambiguity codes of two or three bases
 _COMP = torch.full((256,), ord("N"), dtype=torch.uint8)
 for _a, _b in zip("ATCGNatcgn", "TAGCNtagcn"):
     _COMP[ord(_a)] = ord(_b)
@@ -42,6 +43,19 @@ class EditRates:
     max_indel: int = 12
     big_indel_prob: float = 0.0  # probability that an indel is a large (50..500 bp) event
     min_gap: int = 2           # minimum number of '=' bases between two edits
+
+
+@dataclass
+class Ambiguity:
+    """Bases other than A C G T, as assemblies, GRCh38 and BAM reads carry them.  Drawn from a generator of their own (`seed`): a
+    workload without them draws exactly what it drew before they existed."""
+    seed: int = 1
+    gaps_per_mb: float = 20.0                  # N gaps in the chromosomes (contigs and reads inherit them)
+    gap_len: Tuple[int, int] = (10, 3000)
+    iupac_frac: float = 1e-3                   # isolated IUPAC codes (M R W S Y K V H D B) in the chromosomes
+    contig_join_gaps: bool = True              # the contigs' joins between segments are N runs (scaffold gaps) instead of random bases
+    read_call_frac: float = 2e-3               # N / '=' calls in the reads, per base; written as X ops of the read->contig CIGAR
+    read_eq_share: float = 0.3                 # ... of which '='
 
 
 @dataclass
@@ -65,6 +79,7 @@ class WorkloadConfig:
     read_rates: EditRates = field(default_factory=EditRates)
     seq_fmt: int = abi.SEQ_BAM4
     sorted_reads: bool = False  # reads of a contig in coordinate order, as a coordinate-sorted read->contig BAM delivers them
+    ambiguity: Optional[Ambiguity] = None  # N gaps, IUPAC codes, N / '=' read calls (none in the named workloads)
 
 
 def config(name: str, **over) -> WorkloadConfig:
@@ -161,6 +176,24 @@ def make_reference(length: int, tract_frac: float, gen: torch.Generator, device)
     return seq
 
 
+def add_ambiguity(seq: torch.Tensor, amb: Ambiguity, agen: torch.Generator) -> torch.Tensor:
+    """N gaps and isolated IUPAC codes written into a chromosome (in place)"""
+    device = seq.device
+    L = seq.numel()
+    n_gaps = int(L * amb.gaps_per_mb / 1e6 + torch.rand(1, generator=agen, device=device).item())
+    if n_gaps:
+        start = torch.randint(0, L, (n_gaps,), generator=agen, device=device)
+        glen = torch.randint(amb.gap_len[0], amb.gap_len[1] + 1, (n_gaps,), generator=agen, device=device)
+        gid = torch.repeat_interleave(torch.arange(n_gaps, device=device), glen)
+        pos = (start[gid] + torch.arange(gid.numel(), device=device) - _excl_cumsum(glen)[gid]).clamp_(max=L - 1)
+        seq[pos] = ord("N")
+    n_iu = int(L * amb.iupac_frac)
+    if n_iu:
+        pos = torch.randint(0, L, (n_iu,), generator=agen, device=device)
+        seq[pos] = _lut(_IUPAC2, device)[torch.randint(0, len(_IUPAC2), (n_iu,), generator=agen, device=device)]
+    return seq
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # the edit engine: derive R sequences from intervals of one source sequence
 # ----------------------------------------------------------------------------------------------------------------
@@ -173,9 +206,11 @@ class Mutated:
     seq_off: torch.Tensor    # int64 [R+1]
 
 
-def mutate(source: torch.Tensor, starts: torch.Tensor, spans: torch.Tensor, rates: EditRates, gen: torch.Generator) -> Mutated:
+def mutate(source: torch.Tensor, starts: torch.Tensor, spans: torch.Tensor, rates: EditRates, gen: torch.Generator,
+           calls: Optional[Tuple[Ambiguity, torch.Generator]] = None) -> Mutated:
     """Derive sequence r from source[starts[r] : starts[r]+spans[r]] by random edits; returns the exact alignment
-    (=/X/I/D ops, source as the reference) and the derived bases.  Fully vectorised over r."""
+    (=/X/I/D ops, source as the reference) and the derived bases.  Fully vectorised over r.  `calls`: N / '=' bases at
+    extra X edits, drawn from the second generator (nothing more is drawn from `gen` for them)."""
     device = source.device
     R = starts.numel()
     spans = spans.long()
@@ -213,10 +248,29 @@ def mutate(source: torch.Tensor, starts: torch.Tensor, spans: torch.Tensor, rate
         run_back = torch.cumprod(same.long(), 1).sum(1) - 1  # bases to the left that equal source[gpos]
         off = torch.where(hp, off - run_back, off)
         hp_base = source[gpos]
+    is_call = None
+    if calls is not None and T:
+        amb, agen = calls
+        K2 = int(torch.poisson(torch.full((1,), float(T) * amb.read_call_frac, device=device), generator=agen).item())
+        if K2:
+            v2 = torch.randint(0, T, (K2,), generator=agen, device=device)
+            rid2 = torch.searchsorted(torch.cumsum(spans, 0), v2, right=True)
+            base2 = torch.where(torch.rand(K2, generator=agen, device=device) < amb.read_eq_share, ord("="), ord("N")).to(torch.uint8)
+            one = torch.ones(K2, **i64)
+            new = (rid2, v2 - span_off[rid2], one * OP_X, one, torch.zeros(K2, dtype=torch.bool, device=device), base2)
+            if K:
+                rid, off, kind, ln, hp, hp_base = (torch.cat([x, y]) for x, y in zip((rid, off, kind, ln, hp, hp_base), new))
+            else:
+                rid, off, kind, ln, hp, hp_base = new
+            is_call = torch.cat([torch.zeros(K, dtype=torch.bool, device=device), torch.ones(K2, dtype=torch.bool, device=device)])
+            K += K2
+    if K > 0:
         # order + spacing filter (vectorised: compare with the previous *candidate*)
         key = rid * (int(spans.max().item()) + 1) + off
         order = torch.argsort(key, stable=True)
         rid, off, kind, ln, hp, hp_base = rid[order], off[order], kind[order], ln[order], hp[order], hp_base[order]
+        if is_call is not None:
+            is_call = is_call[order]
         consumed = torch.where(kind == OP_I, torch.zeros_like(ln), ln)
         prev_end = torch.full((K,), -10**9, **i64)
         same_r = torch.zeros(K, dtype=torch.bool, device=device)
@@ -236,6 +290,8 @@ def mutate(source: torch.Tensor, starts: torch.Tensor, spans: torch.Tensor, rate
                 break
             keep[kidx[bad]] = False
         rid, off, kind, ln, hp, hp_base = rid[keep], off[keep], kind[keep], ln[keep], hp[keep], hp_base[keep]
+        if is_call is not None:
+            is_call = is_call[keep]
         consumed = torch.where(kind == OP_I, torch.zeros_like(ln), ln)
         K = rid.numel()
     if K == 0:
@@ -288,6 +344,8 @@ def mutate(source: torch.Tensor, starts: torch.Tensor, spans: torch.Tensor, rate
         run_src[rs + 1] = starts[rid] + off
         run_kind[rs + 1] = torch.where(kind == OP_X, torch.ones_like(kind),
                                        torch.where(hp, torch.full_like(kind, 2), torch.full_like(kind, 3)))
+        if is_call is not None:  # a call: the fixed base ('N' / '=') at an X op
+            run_kind[rs + 1] = torch.where(is_call, torch.full_like(kind, 2), run_kind[rs + 1])
         run_base[rs + 1] = hp_base
     ts = rslot0 + 2 * n_ed
     run_len[ts] = tail_eq
@@ -436,6 +494,12 @@ def generate(cfg: WorkloadConfig, device: str | torch.device = "cpu", reuse: Opt
                                list(reuse.seg_end), reuse.seg_cigar_off, reuse.seg_cigar, reuse.rev_contig_seq, keep_contigs)
 
     chrom_seq = [make_reference(L, cfg.tract_frac, gen, device) for L in cfg.chrom_lens]
+    amb = cfg.ambiguity
+    agen = None
+    if amb is not None:
+        agen = torch.Generator(device=device)
+        agen.manual_seed(amb.seed)
+        chrom_seq = [add_ambiguity(s, amb, agen) for s in chrom_seq]
 
     # ---- contigs ----
     contig_fwd: List[torch.Tensor] = []
@@ -492,6 +556,8 @@ def generate(cfg: WorkloadConfig, device: str | torch.device = "cpu", reuse: Opt
                     gap = int(rng.integers(0, 300)) if n_seg > 1 else 0
                     if gap:
                         pieces.append(_rand_bases(gap, gen, device))
+                        if amb is not None and amb.contig_join_gaps:
+                            pieces[-1].fill_(ord("N"))
                         cpos += gap
                 trail = int(rng.integers(0, 200))
                 if trail:
@@ -533,12 +599,18 @@ def generate(cfg: WorkloadConfig, device: str | torch.device = "cpu", reuse: Opt
     seg_cigar_off[1:] = np.cumsum([len(c) for c in seg_cigs])
     seg_cigar = np.concatenate(seg_cigs) if seg_cigs else np.zeros(0, np.uint32)
     return _generate_reads(cfg, device, gen, rng, chrom_seq, contig_fwd, contig_len, contig_seg_off, seg_chrom, seg_pos, seg_fwd, seg_mapq, seg_start,
-                           seg_end, seg_cigar_off, seg_cigar, rev_contig_seq, keep_contigs)
+                           seg_end, seg_cigar_off, seg_cigar, rev_contig_seq, keep_contigs, agen)
 
 
 def _generate_reads(cfg, device, gen, rng, chrom_seq, contig_fwd, contig_len, contig_seg_off, seg_chrom, seg_pos, seg_fwd, seg_mapq, seg_start,
-                    seg_end, seg_cigar_off, seg_cigar, rev_contig_seq, keep_contigs) -> "Workload":
+                    seg_end, seg_cigar_off, seg_cigar, rev_contig_seq, keep_contigs, agen=None) -> "Workload":
     # ---- reads ----
+    calls = None
+    if cfg.ambiguity is not None and cfg.ambiguity.read_call_frac > 0:
+        if agen is None:
+            agen = torch.Generator(device=device)
+            agen.manual_seed(cfg.ambiguity.seed + cfg.seed)
+        calls = (cfg.ambiguity, agen)
     n_contigs = len(contig_len)
     clen = np.array(contig_len, dtype=np.int64)
     weights = clen / clen.sum()
@@ -559,7 +631,7 @@ def _generate_reads(cfg, device, gen, rng, chrom_seq, contig_fwd, contig_len, co
         if cfg.sorted_reads:
             start, order_ = torch.sort(start)
             rl = rl[order_]
-        m = mutate(contig_fwd[c], start, rl, cfg.read_rates, gen)
+        m = mutate(contig_fwd[c], start, rl, cfg.read_rates, gen, calls)
         is_rev = torch.rand(R, generator=gen, device=device) < 0.5
         # soft clips (random bases) on a fraction of reads, supplementary part on a fraction
         u = torch.rand(R, generator=gen, device=device)
@@ -576,7 +648,7 @@ def _generate_reads(cfg, device, gen, rng, chrom_seq, contig_fwd, contig_len, co
         if n_split:
             bl = torch.randint(1000, 3000, (n_split,), generator=gen, device=device).clamp_(max=Lc - 2)
             bstart = (torch.rand(n_split, generator=gen, device=device) * (Lc - bl).float()).long()
-            mb = mutate(contig_fwd[c], bstart, bl, cfg.read_rates, gen)
+            mb = mutate(contig_fwd[c], bstart, bl, cfg.read_rates, gen, calls)
             b_opp = torch.rand(n_split, generator=gen, device=device) < 0.5
             b_len_s = mb.seq_off[1:] - mb.seq_off[:-1]
             trail[sidx] = 0  # the supplementary part takes the place of the trailing clip

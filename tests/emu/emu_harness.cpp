@@ -528,6 +528,35 @@ extern "C" int emu_finish_batch(const plo_batch_in *in, const plo_finish_in *fin
 // the device comp_base (lift_core.hpp), for an exhaustive comparison with the oracle
 extern "C" int emu_comp_base(int b) { return plo::comp_base(b); }
 
+// The three read decode paths on one window pair: ref[r0 .. r0+15] against read bases q0 .. q0+15 of the read at seq + seq_off
+// (the read as the reference sees it: decoded, complemented and reversed when flipped).  out[0..15]: xor_window16 (lift_core.hpp),
+// out[16..31]: xw16_issue + xw16_decode (lane_core.hpp), out[32..47]: ref byte ^ read_base() for each t whose two positions lie
+// inside their sequences (0 elsewhere).  ok[0], ok[1]: whether the two window paths took the window (false: the caller would fall
+// back to byte probes; their bytes are 0 then).  PLO_SEQ_ASCII or PLO_SEQ_BAM4 only.
+extern "C" void emu_xor_windows(const uint8_t *ref, int ref_len, int r0, const uint8_t *seq, unsigned long long seq_bytes,
+                                unsigned long long seq_off, int len, int fmt, int flip, int q0, uint8_t *out, int *ok) {
+    DevBatch bt;
+    memset(&bt, 0, sizeof(bt));
+    bt.seq = seq;
+    bt.seq_fmt = fmt;
+    bt.seq_bytes = seq_bytes;
+    memset(out, 0, 48);
+    ReadSeq rd = item_read_seq<false>(bt, seq_off, len, flip);
+    unsigned X[4] = {0, 0, 0, 0};
+    ok[0] = xor_window16(ref, ref_len, r0, rd, q0, X) ? 1 : 0;
+    if (ok[0]) memcpy(out, X, 16);
+    alignas(16) static const uint8_t safe[32] = {0};
+    XW16 w;
+    bool miss = false;
+    ok[1] = xw16_issue(true, ref, ref_len, r0, rd, q0, safe, w, miss) ? 1 : 0;
+    if (ok[1]) {
+        xw16_decode(rd, w, X);
+        memcpy(out + 16, X, 16);
+    }
+    for (int t = 0; t < 16; ++t)
+        if (r0 + t >= 0 && r0 + t < ref_len && q0 + t >= 0 && q0 + t < len) out[32 + t] = (uint8_t)(ref[r0 + t] ^ read_base(rd, q0 + t));
+}
+
 // crc32_wave (k_bgzf_crc's wave per BGZF block, inflate.hpp) under the emulator
 extern "C" uint32_t emu_crc32_wave(const uint8_t *p, uint32_t n, unsigned order_seed) {
     uint32_t tab[256];

@@ -116,3 +116,20 @@ def sa_segments(batch: abi.BatchData, lift: abi.BatchResult, item_flag, read_n_l
     text = np.ctypeslib.as_array(text_p, shape=(max(1, int(off[n])),)).copy()[: int(off[n])]
     L.emu_sa_free(off_p, text_p)
     return off, text, item_read
+
+
+def xor_windows(ref: np.ndarray, r0: int, seq: np.ndarray, seq_off: int, read_len: int, seq_fmt: int, flip: bool, q0: int):
+    """the three read decode paths of the device code on one window pair (emu_xor_windows): (X bytes [3, 16], ok [2]).  `ref` and
+    `seq` are used in place, so their addresses set the alignments the window loads see."""
+    L = lib()
+    if not getattr(L, "_xw_bound", False):
+        L.emu_xor_windows.restype = None
+        L.emu_xor_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int)]
+        L._xw_bound = True
+    assert ref.dtype == np.uint8 and seq.dtype == np.uint8 and ref.flags.c_contiguous and seq.flags.c_contiguous
+    out = np.zeros(48, dtype=np.uint8)
+    ok = np.zeros(2, dtype=np.int32)
+    L.emu_xor_windows(ref.ctypes.data, len(ref), r0, seq.ctypes.data, seq.nbytes, seq_off, read_len, seq_fmt, int(flip), q0,
+                      out.ctypes.data_as(C.POINTER(C.c_uint8)), ok.ctypes.data_as(C.POINTER(C.c_int)))
+    return out.reshape(3, 16), ok

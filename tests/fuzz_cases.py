@@ -1,6 +1,7 @@
 """Random adversarial batches for the parity tests: every CIGAR op code (M I D N S H P = X), zero-length ops, edge
 indels, clips inside CIGARs, tiny alphabets (long homologies), inconsistent lengths (LEN_MISMATCH), out-of-range lifted
-positions (PANIC), empty maps, reads crossing several contig segments, reverse-mapped segments."""
+positions (PANIC), empty maps, reads crossing several contig segments, reverse-mapped segments.  Opt-in: reads drawn from an alphabet of their own (N, IUPAC codes, '=', lowercase), BAM 4-bit reads
+encoded from it instead of random bytes."""
 import numpy as np
 
 from portello_amd import abi
@@ -22,9 +23,28 @@ def ref_len(c):
     return int(((c >> 4) * np.isin(t, [0, 2, 3, 7, 8])).sum())
 
 
-def make(seed: int, n_contigs=4, n_reads=40, alphabet=b"ACGT", explicit=False, seq_fmt=abi.SEQ_ASCII):
+BAM4_CODES = b"=ACMGRSVTWYHKDBN"  # the BAM specification's 4-bit base codes
+
+
+def pack_bam4(ascii_bases) -> np.ndarray:
+    """ASCII bases (letters of BAM4_CODES only) -> BAM 4-bit packing, high nibble first"""
+    a = np.frombuffer(bytes(ascii_bases), dtype=np.uint8)
+    lut = np.full(256, 255, dtype=np.uint8)
+    lut[np.frombuffer(BAM4_CODES, dtype=np.uint8)] = np.arange(16, dtype=np.uint8)
+    codes = lut[a]
+    assert (codes != 255).all(), "base without a BAM 4-bit code"
+    if len(codes) % 2:
+        codes = np.append(codes, np.uint8(0))
+    return ((codes[0::2] << 4) | codes[1::2]).astype(np.uint8)
+
+
+def make(seed: int, n_contigs=4, n_reads=40, alphabet=b"ACGT", explicit=False, seq_fmt=abi.SEQ_ASCII, read_alphabet=None,
+         bam4_from_alphabet=False):
+    """`alphabet`: reference and contig bases; `read_alphabet` (default: `alphabet`): read bases.  SEQ_BAM4 reads are random bytes
+    unless `bam4_from_alphabet`, which encodes them from the read alphabet (through BAM4_CODES)."""
     rng = np.random.default_rng(seed)
     alpha = np.frombuffer(alphabet, dtype=np.uint8)
+    ralpha = alpha if read_alphabet is None else np.frombuffer(read_alphabet, dtype=np.uint8)
     n_chroms = 2
     chrom_seq = [alpha[rng.integers(0, len(alpha), size=int(rng.integers(150, 500)))] for _ in range(n_chroms)]
     contig_len, contig_seg_off, rev = [], [0], []
@@ -71,10 +91,12 @@ def make(seed: int, n_contigs=4, n_reads=40, alphabet=b"ACGT", explicit=False, s
         if rng.random() < 0.15:
             rl = int(rng.integers(0, 80))
         nbytes = (rl + 1) // 2 if seq_fmt == abi.SEQ_BAM4 else rl
-        if seq_fmt == abi.SEQ_BAM4:
+        if seq_fmt == abi.SEQ_BAM4 and bam4_from_alphabet:
+            seqs.append(pack_bam4(ralpha[rng.integers(0, len(ralpha), size=rl)].tobytes()))
+        elif seq_fmt == abi.SEQ_BAM4:
             seqs.append(rng.integers(0, 256, size=nbytes).astype(np.uint8))
         else:
-            seqs.append(alpha[rng.integers(0, len(alpha), size=rl)])
+            seqs.append(ralpha[rng.integers(0, len(ralpha), size=rl)])
         read_rev.append(int(rng.random() < 0.5))
         read_len.append(rl)
         read_off.append(off)

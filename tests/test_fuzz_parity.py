@@ -58,6 +58,84 @@ def test_fuzz_emulated_device_algorithm(oracle, seed, monkeypatch):
                     _diff(ref, got, b, f"streaming kernel (rings {mode}, order seed {oseed}): seed {seed} alpha {alpha}")
 
 
+# Bases other than A C G T (reference: N gaps, IUPAC codes; reads: N, IUPAC, '=', lowercase in ASCII): (reference and contig
+# alphabet, read alphabet, read format).  BAM 4-bit reads are encoded from the read alphabet.
+IUPAC = b"ACGTNMRWSYKVHDB"
+AMBIG_CASES = ((b"ACGTN", b"ACGTN=", abi.SEQ_BAM4), (b"ACGTN", b"ACGTNacgtn", abi.SEQ_ASCII), (b"N", b"N", abi.SEQ_BAM4),
+               (b"N", b"N=n", abi.SEQ_ASCII), (b"NA", b"NA=", abi.SEQ_BAM4), (b"NA", b"NAna", abi.SEQ_ASCII),
+               (IUPAC, IUPAC + b"=", abi.SEQ_BAM4), (IUPAC, IUPAC + b"=acgtn", abi.SEQ_ASCII))
+
+
+def _ambig_case(k, seed, n_reads=40):
+    alpha, ralpha, fmt = AMBIG_CASES[k]
+    return fuzz_cases.make(seed, n_reads=n_reads, alphabet=alpha, read_alphabet=ralpha, explicit=(seed % 3 == 0), seq_fmt=fmt,
+                           bam4_from_alphabet=True)
+
+
+def _non_acgt_read_bases(b):
+    """number of read bases that are not A C G T (decoded), and the batch with each of them replaced by C"""
+    import copy
+
+    seq = np.array(b.seq, dtype=np.uint8, copy=True)
+    if b.seq_fmt == abi.SEQ_BAM4:
+        hi, lo = seq >> 4, seq & 15
+        n = int((~np.isin(hi, [1, 2, 4, 8])).sum() + (~np.isin(lo, [1, 2, 4, 8])).sum())  # (counts the pad nibble of odd reads too)
+        seq = ((np.where(np.isin(hi, [1, 2, 4, 8]), hi, 2) << 4) | np.where(np.isin(lo, [1, 2, 4, 8]), lo, 2)).astype(np.uint8)
+    else:
+        bad = ~np.isin(seq, np.frombuffer(b"ACGT", np.uint8))
+        n = int(bad.sum())
+        seq[bad] = ord("C")
+    b2 = copy.copy(b)
+    b2.seq = seq
+    return n, b2
+
+
+def _n_changed(oracle, ix, b, stages=abi.STAGES_ALL):
+    """items whose oracle result changes when the reads' non-ACGT bases become C: homology / shifting crossed those bases"""
+    _, b2 = _non_acgt_read_bases(b)
+    return sum(x != y for x, y in zip(oracle.liftover_batch(ix, b, stages, 1).canonical(), oracle.liftover_batch(ix, b2, stages, 1).canonical()))
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_fuzz_emulated_device_algorithm_ambiguous_bases(oracle, seed, monkeypatch):
+    """the emulated paths of test_fuzz_emulated_device_algorithm (scan, lane, 16-bit regions, heavy lanes, streaming kernel with both
+    ring sizes) on N / IUPAC / '=' / lowercase bases, every stage set, both read formats"""
+    n_changed = 0
+    for k in (seed, seed + 4):
+        ix, b = _ambig_case(k, 300 + seed)
+        n_bad, _ = _non_acgt_read_bases(b)
+        assert n_bad > len(b.seq) // 8
+        n_changed += _n_changed(oracle, ix, b)
+        tag = f"seed {seed} case {AMBIG_CASES[k]}"
+        for stages in STAGE_SETS:
+            ref = oracle.liftover_batch(ix, b, stages, 1)
+            rc, got, _ = emu_lib.liftover_batch(ix, b, stages=stages, cap=256, window=48, big_thresh=10, big_cap=4096)
+            assert rc == 0
+            _diff(ref, got, b, f"{tag} stages {stages}")
+            rc, got, cnt = emu_lib.liftover_batch(ix, b, stages=stages, cap=256, window=48, big_thresh=10, big_cap=4096, lane_max_w=60,
+                                                  lane_capw=1024 if seed % 2 else 160)
+            assert rc == 0 and cnt[23] > 0
+            _diff(ref, got, b, f"lane path: {tag} stages {stages}")
+            if stages & abi.STAGE_LIFTOVER:
+                monkeypatch.setenv("PLO_EMU_H16", "1")
+                rc, got, cnt = emu_lib.liftover_batch(ix, b, stages=stages, cap=256, window=48, big_thresh=10, big_cap=4096, lane_max_w=60,
+                                                      lane_capw=1024 if seed % 2 else 160, order_seed=(0, 21 + seed)[seed % 2])
+                monkeypatch.delenv("PLO_EMU_H16")
+                assert rc == 0 and cnt[23] > 0
+                _diff(ref, got, b, f"lane path, 16-bit regions: {tag} stages {stages}")
+            rc, got, cnt = emu_lib.liftover_batch(ix, b, stages=stages, cap=256, window=48, big_thresh=10, big_cap=4096, lane_max_w=12,
+                                                  lane_capw=1024, lane_heavy_per=(64, 5)[seed % 2])
+            assert rc == 0 and cnt[23] < got.n_items
+            _diff(ref, got, b, f"heavy lane path: {tag} stages {stages}")
+            if stages == abi.STAGES_ALL:
+                for mode in (1, 2):
+                    rc, got, cnt = emu_lib.liftover_batch(ix, b, stages=stages, cap=256, window=48, big_thresh=10, big_cap=4096, lane_max_w=12,
+                                                          lane_capw=1024, lane_heavy_per=(64, 5)[seed % 2], lane_stream=mode, order_seed=seed)
+                    assert rc == 0 and cnt[23] < got.n_items
+                    _diff(ref, got, b, f"streaming kernel (rings {mode}): {tag}")
+    assert n_changed > 0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("h16", ["0", "1"])
 def test_fuzz_hip(oracle, h16, monkeypatch):
@@ -103,3 +181,32 @@ def test_fuzz_hip_heavy_lane_kernel(oracle, monkeypatch, per, variant):
         eng.close()
         index.close()
     assert heavy > 40 * len(STAGE_SETS) * 20  # (most items of every batch went through the heavy-lane kernel)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["default", "h16", "g", "g_w3", "stream"])
+def test_fuzz_hip_ambiguous_bases(oracle, monkeypatch, route):
+    """the adversarial batches on N / IUPAC / '=' / lowercase bases through the C ABI, every stage set: the default routing, 16-bit
+    regions, and every instantiation of the heavy-item lane kernel with nearly every item in the heavy classes"""
+    from variants import HEAVY_VARIANTS
+
+    if route == "h16":
+        monkeypatch.setenv("PLO_LANE_H16", "1")
+    elif route != "default":
+        for k, v in HEAVY_VARIANTS[route].items():
+            monkeypatch.setenv(k, v)
+        monkeypatch.setenv("PLO_LANE_HEAVY_MIN", "0")
+        monkeypatch.setenv("PLO_LANE_MAX_W", "12")
+    taken = 0
+    for seed in range(16):
+        ix, b = _ambig_case(seed % len(AMBIG_CASES), 3000 + seed, n_reads=120)
+        index = api.Index(ix)
+        eng = api.Engine(index)
+        for stages in STAGE_SETS:
+            got = eng.liftover_batch(b, stages)
+            t = eng.timing()
+            taken += int(t.n_lane_items if route in ("default", "h16") else t.n_heavy_lane_items)
+            _diff(oracle.liftover_batch(ix, b, stages, 1), got, b, f"{route}: seed {seed} case {AMBIG_CASES[seed % len(AMBIG_CASES)]} stages {stages}")
+        eng.close()
+        index.close()
+    assert taken > 16 * len(STAGE_SETS) * 20
