@@ -110,6 +110,21 @@ plo_status plo_bam_window_batch_sparse(plo_bam_window *w, uint32_t margin, plo_b
 plo_status plo_bam_window_batch_sparse_strand(plo_bam_window *w, uint32_t margin, const plo_index_desc *index, plo_batch_in *batch,
                                               plo_finish_in *fin);
 
+/* The dense batch as VIEWS into the window's own copy of the records, for the path that assembles the output records on the device
+ * (plo_records_build_dev): `raw` describes the window's stretch of the BAM stream (page-locked when a HIP device is usable) and the
+ * offset of every primary record's block_size word in it; batch->seq = fin->qual = raw->raw, and batch->read_seq_off /
+ * fin->read_qual_off are the byte offsets of the reads' packed bases / qualities inside it (dense PLO_SEQ_BAM4 offsets are
+ * byte-granular).  A caller uploads `raw` ONCE and hands the same device buffer to plo_batch_in::seq, plo_finish_in::qual and
+ * plo_records_in::records; bases and qualities are not gathered into arrays of their own.  Segments, CIGARs and flags are built as in
+ * plo_bam_window_batch.  All pointers are owned by the window. */
+typedef struct plo_window_raw {
+    const uint8_t *raw;
+    uint64_t raw_bytes;
+    uint32_t n_reads;
+    const uint64_t *read_rec_off; /* [n_reads] */
+} plo_window_raw;
+plo_status plo_bam_window_batch_raw(plo_bam_window *w, plo_batch_in *batch, plo_finish_in *fin, plo_window_raw *raw);
+
 /* The same transformation for a batch that already exists with dense PLO_SEQ_BAM4 bases in host memory (seg_read non-decreasing).
  * `out` needs plo_sparse_seq_bound(dense) bytes (page-locked memory from plo_host_alloc makes the upload faster), out_read_off
  * n_reads entries.  *sparse = *dense with seq / seq_bytes / seq_fmt / read_seq_off replaced and seq_full / read_seq_full_off

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 6 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events */
+#define PLO_API_VERSION 7 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -339,6 +339,45 @@ typedef struct plo_sa_out {
 } plo_sa_out;
 
 plo_status plo_sa_segments_dev(plo_ctx *ctx, const plo_sa_in *in, plo_sa_out *out);
+
+/* ---- Output records (device-resident) ---------------------------------------------------------------------------
+ * Consumes the results of the preceding plo_liftover_batch_dev (+ plo_compact_output_dev), plo_finish_batch_dev and
+ * plo_sa_segments_dev on the same context and writes the window's output BAM records -- for every read, in order, its lifted
+ * records (item order) or, when nothing lifted and !is_target_region, the unmapped copy -- byte for byte what
+ * plo_records_build (portello_bam.h) writes from host copies: clone_record with NM / SA / PS / ZM removed
+ * (src/read_alignment_scanner.rs:105-118), PS / ZM :254-268, pos / CIGAR / flags / bin :270-282, reversed bases and qualities
+ * :125-133, unmapped copy :317-335, SA :348-364, serialised as bam_write1 does (CG:B,I beyond 65535 CIGAR ops).
+ * `records` holds the window's stretch of the BAM stream as it stands (plo_bam_window_batch_raw, portello_bam.h: the batch's `seq` and
+ * the finishing's `qual` may be views into the same buffer).  PS:Z labels are the @SQ names of the read->contig BAM; the strand suffix
+ * comes from the context's index, the SA labels are already inside the SA text.  The label table is trusted as plo_sa_in's is
+ * (contig_name_off non-decreasing and inside contig_names): the caller makes it from the BAM header, it is not data of the stream.
+ * Every record is checked on the device before a byte is written: a read_rec_off or a record's block_size / l_qname / n_cigar /
+ * l_seq that points outside `records`, or an l_seq that differs from the batch's read_seq_len -> PLO_ERR_INVALID_ARG, nothing written.
+ * Called out of order (no finish / SA result on the context), or after a batch with sparse or ASCII bases -> PLO_ERR_INVALID_ARG.
+ * The stream is waited for twice: once for the sizes and once behind the emit kernel, for the event times -- like
+ * plo_finish_batch_dev and plo_sa_segments_dev the call returns when its kernels are through, so a caller cannot put the download
+ * of one window under the emit kernel of the same context.  All pointers are device pointers; outputs are owned by the context, valid until its next call. */
+typedef struct plo_records_in {
+    const uint8_t *records;          /* the window's records as they stand: block_size word + block_size bytes each   */
+    uint64_t records_bytes;
+    const uint64_t *read_rec_off;    /* [n_reads] offset of primary record r's block_size word inside `records`       */
+    uint32_t n_contigs;              /* at least the index's contigs                                                   */
+    const uint32_t *contig_name_off; /* [n_contigs + 1] byte offsets into contig_names                                 */
+    const uint8_t *contig_names;     /* concatenated labels, no terminators                                            */
+    int32_t is_target_region;        /* src/read_alignment_scanner.rs:318-320: no unmapped copy                        */
+} plo_records_in;
+
+typedef struct plo_records_out {
+    const uint8_t *bytes;            /* records, each prefixed by its block_size: what plo_bam_write takes             */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    const uint64_t *record_off;      /* [n_records + 1]                                                                */
+    uint32_t n_lifted, n_unmapped_copies;
+    float records_ms;                /* HIP-event time of this call's work on the stream: plan + scans + the 40 bytes of sizes
+                                        copied back, then (behind the host's look at them) emit + 8 bytes up for record_off's end */
+} plo_records_out;
+
+plo_status plo_records_build_dev(plo_ctx *ctx, const plo_batch_in *in, const plo_records_in *rin, plo_records_out *out);
 
 /* (plo_finish_batch_dev returns PLO_ERR_DATA when an item of the batch ended LEN_MISMATCH or PANIC -- the reference aborts
    there, :207-229 -- and leaves is_target_region handling (:318-320: no unmapped copy) to the caller.)

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 6  # include/portello_liftover.h
+PLO_API_VERSION = 7  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -171,6 +171,20 @@ class PloSaIn(C.Structure):
 
 class PloSaOut(C.Structure):
     _fields_ = [("n_items", C.c_uint32), ("item_sa_off", _u32p), ("sa_text", _u8p), ("sa_bytes", C.c_uint64), ("sa_ms", C.c_float)]
+
+
+class PloRecordsIn(C.Structure):
+    _fields_ = [("records", _u8p), ("records_bytes", C.c_uint64), ("read_rec_off", _u64p), ("n_contigs", C.c_uint32),
+                ("contig_name_off", _u32p), ("contig_names", _u8p), ("is_target_region", C.c_int32)]
+
+
+class PloRecordsOut(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("n_lifted", C.c_uint32),
+                ("n_unmapped_copies", C.c_uint32), ("records_ms", C.c_float)]
+
+
+class PloWindowRaw(C.Structure):  # include/portello_bam.h
+    _fields_ = [("raw", _u8p), ("raw_bytes", C.c_uint64), ("n_reads", C.c_uint32), ("read_rec_off", _u64p)]
 
 
 FINISH_ITEM_FIELDS = [("item_flag", np.uint16), ("item_bin", np.uint16), ("item_ref_end", np.int64), ("item_is_primary", np.uint8),

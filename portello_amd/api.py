@@ -76,6 +76,8 @@ def load_library(path: Optional[str] = None):
     L.plo_sa_segments_dev.argtypes = [vp, C.POINTER(abi.PloSaIn), C.POINTER(abi.PloSaOut)]
     L.plo_finish_batch_dev.restype = C.c_int
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
+    L.plo_records_build_dev.restype = C.c_int
+    L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_ctx_sync.restype = C.c_int
     L.plo_ctx_sync.argtypes = [vp]
     L.plo_ctx_download.restype = C.c_int
@@ -217,6 +219,13 @@ class Engine:
         """SA-tag segments of the last liftover + finish result (plo_sa_segments_dev); device pointers."""
         out = abi.PloSaOut()
         self._check(self.lib.plo_sa_segments_dev(self.handle, C.byref(sa_in), C.byref(out)), "plo_sa_segments_dev")
+        return out
+
+    def records_build_dev(self, desc: abi.PloBatchIn, rin: abi.PloRecordsIn) -> abi.PloRecordsOut:
+        """The window's output BAM records assembled on the device from the last liftover + finish + SA results
+        (plo_records_build_dev); device pointers in and out."""
+        out = abi.PloRecordsOut()
+        self._check(self.lib.plo_records_build_dev(self.handle, C.byref(desc), C.byref(rin), C.byref(out)), "plo_records_build_dev")
         return out
 
     def download(self, dev_ptr, dtype, count: int) -> np.ndarray:

@@ -62,6 +62,8 @@ def lib():
         L.plo_bam_set_device_inflate.argtypes = [vp, C.c_int]
         L.plo_bam_window_batch_sparse.restype = C.c_int
         L.plo_bam_window_batch_sparse.argtypes = [vp, C.c_uint32, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn)]
+        L.plo_bam_window_batch_raw.restype = C.c_int
+        L.plo_bam_window_batch_raw.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloWindowRaw)]
         L.plo_sparse_seq_bound.restype = C.c_uint64
         L.plo_sparse_seq_bound.argtypes = [C.POINTER(abi.PloBatchIn)]
         L.plo_sparse_seq_pack.restype = C.c_int
@@ -158,6 +160,14 @@ class Window:
             _check(lib().plo_bam_window_batch(self.handle, C.byref(b), C.byref(f) if with_finish else None), "plo_bam_window_batch")
         self._batch = b
         return (b, f) if with_finish else b
+
+    def batch_raw(self):
+        """(plo_batch_in, plo_finish_in, plo_window_raw) with the bases and qualities as views into the window's own copy of the records
+        (plo_bam_window_batch_raw): for the route that uploads the records once and assembles the output on the device"""
+        b, f, r = abi.PloBatchIn(), abi.PloFinishIn(), abi.PloWindowRaw()
+        _check(lib().plo_bam_window_batch_raw(self.handle, C.byref(b), C.byref(f), C.byref(r)), "plo_bam_window_batch_raw")
+        self._batch = b
+        return b, f, r
 
     def batch_data(self) -> abi.BatchData:
         """numpy copy of the batch (for the oracle / the host-buffer entry point)"""

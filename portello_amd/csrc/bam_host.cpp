@@ -505,11 +505,23 @@ extern "C" plo_status plo_bam_window_batch_sparse_strand(plo_bam_window *w, uint
         return fail(PLO_ERR_INVALID_ARG, "plo_bam_window_batch_sparse_strand: the index description lacks its segment arrays");
     return window_batch(w, batch, fin, (int)std::min<uint32_t>(margin, 1u << 20), index);
 }
+// sparse_margin -2: dense bases and qualities as views into w->raw (nothing gathered)
+extern "C" plo_status plo_bam_window_batch_raw(plo_bam_window *w, plo_batch_in *batch, plo_finish_in *fin, plo_window_raw *raw) {
+    if (!w || !batch || !fin || !raw) return PLO_ERR_INVALID_ARG;
+    memset(raw, 0, sizeof(*raw));
+    plo_status st = window_batch(w, batch, fin, -2);
+    if (st != PLO_OK) return st;
+    raw->raw = w->raw.data();
+    raw->raw_bytes = w->raw.size();
+    raw->n_reads = w->n_records();
+    raw->read_rec_off = w->rec_at.data();
+    return PLO_OK;
+}
 
 static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finish_in *fin, int sparse_margin, const plo_index_desc *ixd) {
     if (!w || !batch) return PLO_ERR_INVALID_ARG;
     memset(batch, 0, sizeof(*batch));
-    const bool sparse = sparse_margin >= 0;
+    const bool sparse = sparse_margin >= 0, views = sparse_margin == -2;
     const uint32_t n = w->n_records();
     // pass 1 (parallel): segments of every read; sizes
     std::vector<std::vector<SaSeg>> segs(n);
@@ -552,7 +564,9 @@ static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finis
     uint8_t *rev = (uint8_t *)w->b_rev.ensure(std::max<size_t>(n, 1));
     uint32_t *rlen = (uint32_t *)w->b_len.ensure(std::max<size_t>(n, 1) * 4);
     uint64_t *soff = (uint64_t *)w->b_soff.ensure(std::max<size_t>(n, 1) * 8);
-    uint8_t *seq = sparse ? nullptr : (uint8_t *)w->b_seq.ensure(std::max<uint64_t>(n_seqb[n], 16));
+    static uint8_t no_raw[16];
+    uint8_t *raw_base = w->raw.data() ? w->raw.data() : no_raw;  // (a window without records)
+    uint8_t *seq = sparse ? nullptr : views ? raw_base : (uint8_t *)w->b_seq.ensure(std::max<uint64_t>(n_seqb[n], 16));
     uint64_t *full_off = sparse ? (uint64_t *)w->b_full_off.ensure(std::max<size_t>(n, 1) * 8) : soff;
     uint32_t *seg_read = (uint32_t *)w->b_seg_read.ensure(std::max<size_t>(ns, 1) * 4);
     uint32_t *seg_contig = (uint32_t *)w->b_seg_contig.ensure(std::max<size_t>(ns, 1) * 4);
@@ -561,7 +575,7 @@ static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finis
     uint32_t *coff = (uint32_t *)w->b_coff.ensure(((size_t)ns + 1) * 4);
     uint32_t *cigar = (uint32_t *)w->b_cigar.ensure(std::max<uint64_t>(n_ops[n], 1) * 4);
     uint16_t *flags = (uint16_t *)w->b_flags.ensure(std::max<size_t>(n, 1) * 2);
-    uint8_t *qual = fin ? (uint8_t *)w->b_qual.ensure(std::max<uint64_t>(n_qual[n], 16)) : nullptr;
+    uint8_t *qual = !fin ? nullptr : views ? raw_base : (uint8_t *)w->b_qual.ensure(std::max<uint64_t>(n_qual[n], 16));
     uint64_t *qoff = fin ? (uint64_t *)w->b_qoff.ensure(std::max<size_t>(n, 1) * 8) : nullptr;
     if (!rev || !rlen || !soff || !full_off || (!sparse && !seq) || !seg_read || !seg_contig || !seg_pos || !seg_fwd || !coff || !cigar || !flags || (fin && (!qual || !qoff)))
         return fail(PLO_ERR_OUT_OF_MEMORY, "out of host memory for the window's batch");
@@ -573,11 +587,15 @@ static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finis
         flags[i] = rec.flag();
         if (sparse) {  // the complete bases stay where they are, inside the window's copy of the records
             full_off[i] = (uint64_t)(rec.seq() - w->raw.data());
+        } else if (views) {  // the bases and qualities stay inside the records too: the caller uploads w->raw as it stands
+            soff[i] = (uint64_t)(rec.seq() - w->raw.data());
         } else {
             soff[i] = n_seqb[i];
             memcpy(seq + n_seqb[i], rec.seq(), (size_t)(n_seqb[i + 1] - n_seqb[i]));
         }
-        if (fin) {
+        if (fin && views) {
+            qoff[i] = (uint64_t)(rec.qual() - w->raw.data());
+        } else if (fin) {
             qoff[i] = n_qual[i];
             memcpy(qual + n_qual[i], rec.qual(), rec.l_seq());
         }
@@ -596,7 +614,7 @@ static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finis
         }
     });
     coff[ns] = (uint32_t)n_ops[n];
-    uint64_t seq_bytes = n_seqb[n];
+    uint64_t seq_bytes = views ? w->raw.size() : n_seqb[n];
     if (sparse) {
         // pass 3 (parallel): granule masks from the CIGARs just written, then headers + granules straight from the records
         std::vector<uint64_t> woff((size_t)n + 1, 0), boff((size_t)n + 1, 0);
@@ -640,7 +658,7 @@ static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finis
         fin->read_flags = flags;
         fin->qual = qual;
         fin->read_qual_off = qoff;
-        fin->qual_bytes = n_qual[n];
+        fin->qual_bytes = views ? w->raw.size() : n_qual[n];
     }
     w->batch_kind = sparse ? 2 : 1;
     return PLO_OK;

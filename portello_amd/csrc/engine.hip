@@ -39,6 +39,7 @@
 
 #include "enumerate.hpp"
 #include "finish_core.hpp"
+#include "records_core.hpp"
 #include "index_pack.hpp"
 #include "inflate.hpp"
 #include "lift_core.hpp"
@@ -1283,6 +1284,28 @@ __global__ __launch_bounds__(256) void k_revcomp(DevBatch bt, DevWork wk, DevFin
     }
 }
 
+// ---- output records (records_core.hpp) -----------------------------------------------------------------------------------
+// plan: a wave per read (the aux walk looks for a string's NUL 64 bytes per step)
+__global__ __launch_bounds__(256) void k_rec_plan(DevBatch bt, DevWork wk, DevRecords d) {
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r < bt.n_reads) records_plan_read(bt, wk, d, r);  // (wave-uniform)
+}
+// the 64-bit exclusive scans of the reads' bytes (blockIdx.y 0), record counts (1) and unmapped copies (2): a wave per 512 values
+__global__ __launch_bounds__(64) void k_rec_scan_sums(const unsigned long long *in, uint32_t n, uint32_t nb, unsigned long long *partial) {
+    rec_scan_sums(in + (size_t)blockIdx.y * n, n, blockIdx.x, partial + (size_t)blockIdx.y * nb);
+}
+__global__ __launch_bounds__(64) void k_rec_scan_partials(unsigned long long *partial, uint32_t n, uint32_t nb, unsigned long long *out) {
+    rec_scan_partials(partial + (size_t)blockIdx.x * nb, nb, out + (size_t)blockIdx.x * ((size_t)n + 1) + n);
+}
+__global__ __launch_bounds__(64) void k_rec_scan_apply(const unsigned long long *in, uint32_t n, uint32_t nb, const unsigned long long *partial, unsigned long long *out) {
+    rec_scan_apply(in + (size_t)blockIdx.y * n, n, blockIdx.x, partial + (size_t)blockIdx.y * nb, out + (size_t)blockIdx.y * ((size_t)n + 1));
+}
+// emit: a workgroup per read at a time.  HBM-bound: per 15 kb record ~22.5 kB in, the same out.  VEC false: the plain byte copy (A/B)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_rec_emit(DevBatch bt, DevWork wk, DevRecords d) {
+    for (uint32_t r = blockIdx.x; r < bt.n_reads; r += gridDim.x) records_emit_read<VEC>(bt, wk, d, r, (int)threadIdx.x, (int)blockDim.x);
+}
+
 // ---- BGZF inflate (inflate.hpp): every block of a chunk of the BAM stream at once, one wave per block ----------------------
 struct BgzfBlk {
     unsigned long long coff, uoff;  // offsets of the block's deflate data / inflated bytes inside the chunk buffers
@@ -1459,10 +1482,13 @@ struct plo_ctx {
     std::string err;
     // workspace
     DevBuf f_flag, f_bin, f_end, f_prim, f_isoff, f_iqoff, f_iread, f_nl, f_pitem, f_uflag, f_rsoff, f_rqoff, f_su, f_qu, f_soff,
-        f_qoff, f_rseq, f_rqual, f_fflag, f_frank, f_flist, sa_len, sa_off, sa_text;
+        f_qoff, f_rseq, f_rqual, f_fflag, f_frank, f_flist, sa_len, sa_off, sa_text, r_plan, r_size, r_start, r_partial, r_recoff, r_out, r_err;
+    HostBuf h_rec;
     DevWork last_wk{};
     DevBatch last_bt{};
-    bool have_last = false, have_finish = false;
+    bool have_last = false, have_finish = false, have_sa = false;
+    bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
+    hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf item_region, lane_groups;
     DevBuf misc, whist, cls_partial, lane_scratch, item_cls, retry_list, perm, nin_p, seg_reflen, seg_readlen, seg_nm, seg_cnt, seg_off, scan_partial, item_seg, item_cseg, item_nin, op_prefix, counters, big_list, huge_list, scratch, tile_lo, verr, miss_list, miss_info, miss_vals, miss_seq_off, miss_side;
@@ -1796,6 +1822,7 @@ plo_status plo_ctx_create(const plo_index *ix, void *hip_stream, plo_ctx **out) 
     if (const char *e = getenv("PLO_SCAN_CHAIN")) c->scan_chain = atoi(e) != 0;
     if (const char *e = getenv("PLO_FAST_LAUNCH_BOUND")) c->fast_launch_bound = atoi(e) != 0;
     if (const char *e = getenv("PLO_FAST_FUSE")) c->fast_fuse = atoi(e) != 0;
+    if (const char *e = getenv("PLO_RECORDS_BYTECOPY")) c->rec_bytecopy = atoi(e) != 0;
     if (const char *e = getenv("PLO_PHASE_EVENTS")) c->phase_events = atoi(e) != 0;
     if (const char *e = getenv("PLO_LANE_CAPW")) c->lane_capw = std::min(40000, std::max(64, atoi(e))) & ~3;
     if (c->lane_max_w + LANE_SLACK > c->lane_capw) c->lane_max_w = c->lane_capw - LANE_SLACK;
@@ -1812,7 +1839,7 @@ void plo_ctx_destroy(plo_ctx *c) {
     (void)hipSetDevice(c->ix->device);
     (void)hipStreamSynchronize(c->stream);
     DevBuf *bufs[] = {&c->f_flag, &c->f_bin, &c->f_end, &c->f_prim, &c->f_isoff, &c->f_iqoff, &c->f_iread, &c->f_nl, &c->f_pitem,
-                      &c->f_uflag, &c->f_rsoff, &c->f_rqoff, &c->f_su, &c->f_qu, &c->f_soff, &c->f_qoff, &c->f_rseq, &c->f_rqual, &c->f_fflag, &c->f_frank, &c->f_flist, &c->sa_len, &c->sa_off, &c->sa_text,
+                      &c->f_uflag, &c->f_rsoff, &c->f_rqoff, &c->f_su, &c->f_qu, &c->f_soff, &c->f_qoff, &c->f_rseq, &c->f_rqual, &c->f_fflag, &c->f_frank, &c->f_flist, &c->sa_len, &c->sa_off, &c->sa_text, &c->r_plan, &c->r_size, &c->r_start, &c->r_partial, &c->r_recoff, &c->r_out, &c->r_err,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1822,12 +1849,14 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 5; ++i)
         if (c->fev[i]) (void)hipEventDestroy(c->fev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->rev[i]) (void)hipEventDestroy(c->rev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -2662,6 +2691,7 @@ plo_status plo_liftover_batch_dev(plo_ctx *c, const plo_batch_in *in, uint32_t s
     c->last_bt = bt;
     c->have_last = true;
     c->have_finish = false;
+    c->have_sa = false;
     return PLO_OK;
 }
 
@@ -2841,6 +2871,7 @@ static plo_status liftover_fast(plo_ctx *c, const plo_batch_in *in, uint32_t sta
     c->last_bt = bt;
     c->have_last = true;
     c->have_finish = false;
+    c->have_sa = false;
     return PLO_OK;
 }
 
@@ -2856,6 +2887,8 @@ plo_status plo_finish_batch_dev(plo_ctx *c, const plo_batch_in *in, const plo_fi
         c->err = "plo_finish_batch_dev: the batch came with sparse bases (PLO_SEQ_BAM4_SPARSE); the flipped sequences are written from complete ones";
         return PLO_ERR_INVALID_ARG;
     }
+    c->have_finish = false;
+    c->have_sa = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     hipStream_t st = c->stream;
     for (int i = 0; i < 3; ++i)
@@ -3017,6 +3050,132 @@ plo_status plo_sa_segments_dev(plo_ctx *c, const plo_sa_in *in, plo_sa_out *out)
     out->item_sa_off = c->sa_off.as<uint32_t>();
     out->sa_text = sa.text;
     out->sa_bytes = bytes;
+    c->have_sa = true;
+    return PLO_OK;
+}
+
+plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_records_in *rin, plo_records_out *out) {
+    if (!c || !in || !rin || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    c->err.clear();
+    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
+        c->err = "plo_records_build_dev: the batch came with sparse or ASCII bases; the records are written from complete BAM 4-bit bases (PLO_SEQ_BAM4)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
+        c->err = "plo_records_build_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_finish) {
+        c->err = "plo_records_build_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_sa) {
+        c->err = "plo_records_build_dev: no SA text on the context: call plo_sa_segments_dev behind the finishing first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (rin->n_contigs < c->ix->d.n_contigs || !rin->contig_name_off || (!rin->contig_names && rin->n_contigs) ||
+        (in->n_reads && (!rin->records || !rin->read_rec_off))) {
+        c->err = "plo_records_in: the records, their offsets and one label per contig of the index are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->rev[i]) HIP_TRY(c, hipEventCreate(&c->rev[i]));
+    const DevWork &wk = c->last_wk;
+    const DevBatch &bt = c->last_bt;
+    const uint32_t nr = bt.n_reads, nb = std::max(1u, (nr + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    const size_t b = std::max(1u, nr);
+    HIP_TRY(c, c->r_plan.ensure(b * REC_PLAN_WORDS * 4));
+    HIP_TRY(c, c->r_size.ensure(3 * b * 8));
+    HIP_TRY(c, c->r_start.ensure(3 * (b + 1) * 8));
+    HIP_TRY(c, c->r_partial.ensure(3 * (size_t)nb * 8));
+    HIP_TRY(c, c->r_err.ensure(REC_ERR_N * 4));
+    HIP_TRY(c, c->h_rec.ensure(64));
+    DevRecords d;
+    memset(&d, 0, sizeof(d));
+    d.records = rin->records;
+    d.records_bytes = rin->records_bytes;
+    d.read_rec_off = rin->read_rec_off;
+    d.contig_name_off = rin->contig_name_off;
+    d.contig_names = rin->contig_names;
+    d.is_target_region = rin->is_target_region;
+    d.item_flag = c->f_flag.as<uint16_t>();
+    d.item_bin = c->f_bin.as<uint16_t>();
+    d.item_ref_end = c->f_end.as<int64_t>();
+    d.item_seq_off = c->f_isoff.as<uint64_t>();
+    d.item_qual_off = c->f_iqoff.as<uint64_t>();
+    d.item_read = c->f_iread.as<uint32_t>();
+    d.read_n_lifted = c->f_nl.as<uint32_t>();
+    d.read_unmapped_flag = c->f_uflag.as<uint16_t>();
+    d.read_seq_off = c->f_rsoff.as<uint64_t>();
+    d.read_qual_off = c->f_rqoff.as<uint64_t>();
+    d.rev_seq = c->f_rseq.as<uint8_t>();
+    d.rev_qual = c->f_rqual.as<uint8_t>();
+    d.sa_off = c->sa_off.as<uint32_t>();
+    d.sa_text = c->sa_text.as<uint8_t>();
+    d.cs_is_fwd = c->ix->d.cs_is_fwd;
+    d.contig_seg_off = c->ix->d.contig_seg_off;
+    d.plan = c->r_plan.as<uint32_t>();
+    d.size = c->r_size.as<unsigned long long>();
+    d.start = c->r_start.as<unsigned long long>();
+    d.err = c->r_err.as<unsigned>();
+    unsigned long long *start = c->r_start.as<unsigned long long>();
+    unsigned long long *h = c->h_rec.as<unsigned long long>();
+    memset(h, 0, 64);
+    HIP_TRY(c, hipMemsetAsync(c->r_err.p, 0, REC_ERR_N * 4, st));
+    HIP_TRY(c, hipEventRecord(c->rev[0], st));
+    if (nr) {
+        hipLaunchKernelGGL(k_rec_plan, dim3((nr + 3) / 4), dim3(256), 0, st, bt, wk, d);
+        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 3), dim3(64), 0, st, (const unsigned long long *)d.size, nr, nb, c->r_partial.as<unsigned long long>());
+        hipLaunchKernelGGL(k_rec_scan_partials, dim3(3), dim3(64), 0, st, c->r_partial.as<unsigned long long>(), nr, nb, start);
+        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 3), dim3(64), 0, st, (const unsigned long long *)d.size, nr, nb, (const unsigned long long *)c->r_partial.as<unsigned long long>(), start);
+        HIP_TRY(c, hipGetLastError());
+        // the one round trip: total bytes, records, unmapped copies, and the bounds checks
+        HIP_TRY(c, hipMemcpyAsync(h, start + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h + 1, start + (size_t)nr + 1 + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h + 2, start + 2 * ((size_t)nr + 1) + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h + 4, c->r_err.p, REC_ERR_N * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipEventRecord(c->rev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const unsigned *herr = (const unsigned *)(h + 4);
+    if (herr[REC_ERR_OFFSET] || herr[REC_ERR_BLOCK] || herr[REC_ERR_LAYOUT] || herr[REC_ERR_SEQLEN]) {
+        c->err = "plo_records_build_dev: " + std::to_string(herr[REC_ERR_OFFSET]) + " read_rec_off beyond records_bytes, " + std::to_string(herr[REC_ERR_BLOCK]) +
+                 " block_size running past the end of `records`, " + std::to_string(herr[REC_ERR_LAYOUT]) + " l_qname / n_cigar / l_seq pointing outside their record, " +
+                 std::to_string(herr[REC_ERR_SEQLEN]) + " l_seq different from the batch's read_seq_len; nothing was written";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const unsigned long long n_bytes = h[0], n_rec = h[1];
+    if (n_rec > 0xfffffffeull) {
+        c->err = "plo_records_build_dev: more than 2^32 - 2 output records in one window";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, c->r_out.ensure(std::max<unsigned long long>(n_bytes, 16)));
+    HIP_TRY(c, c->r_recoff.ensure((n_rec + 1) * 8));
+    d.out = c->r_out.as<uint8_t>();
+    d.record_off = c->r_recoff.as<uint64_t>();
+    HIP_TRY(c, hipEventRecord(c->rev[2], st));
+    if (n_rec) {
+        const uint32_t nblk = std::min<uint32_t>(nr, (uint32_t)c->n_cus * 8u);
+        if (c->rec_bytecopy) hipLaunchKernelGGL(k_rec_emit<false>, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        else hipLaunchKernelGGL(k_rec_emit<true>, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(d.record_off + n_rec, &h[0], 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->rev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float a_ms = 0, b_ms = 0;
+    (void)hipEventElapsedTime(&a_ms, c->rev[0], c->rev[1]);
+    (void)hipEventElapsedTime(&b_ms, c->rev[2], c->rev[3]);
+    out->records_ms = a_ms + b_ms;
+    out->bytes = d.out;
+    out->n_bytes = n_bytes;
+    out->n_records = (uint32_t)n_rec;
+    out->record_off = d.record_off;
+    out->n_unmapped_copies = (uint32_t)h[2];
+    out->n_lifted = (uint32_t)(n_rec - h[2]);
     return PLO_OK;
 }
 

@@ -302,3 +302,116 @@ class HostResults:
             self.sa.sa_ms = so.sa_ms
         if pending:
             torch.cuda.current_stream().synchronize()  # one wait for all the copies
+
+
+# ---- a BAM window's records on the device as they stand, the output records assembled there (pipeline.run_bam_to_bam, device_records) ----
+
+@dataclass
+class UploadedRawWindow:
+    """the window's stretch of the BAM stream in HBM, ONE upload: the batch's bases, the finishing's qualities and the source records of
+    plo_records_build_dev are views into `raw`; keeps the tensors alive"""
+    raw: torch.Tensor
+    raw_bytes: int
+    batch: DeviceBatch
+    flags: torch.Tensor
+    qual_off: torch.Tensor
+    rec_off: torch.Tensor
+
+    def finish_in(self) -> abi.PloFinishIn:
+        return abi.PloFinishIn(_p(self.flags, C.c_uint16), _p(self.raw, C.c_uint8), _p(self.qual_off, C.c_uint64), self.raw_bytes)
+
+    def records_in(self, labels, is_target_region: bool = False) -> abi.PloRecordsIn:
+        """labels: contig_labels(...) of the read->contig BAM's @SQ names"""
+        n, t_off, t_blob = labels
+        return abi.PloRecordsIn(_p(self.raw, C.c_uint8), self.raw_bytes, _p(self.rec_off, C.c_uint64), n, _p(t_off, C.c_uint32), _p(t_blob, C.c_uint8),
+                                1 if is_target_region else 0)
+
+
+def upload_raw_window(desc: abi.PloBatchIn, fin: abi.PloFinishIn, raw: abi.PloWindowRaw, dev) -> UploadedRawWindow:
+    """copies what bam.Window.batch_raw() describes to the device on torch's current stream: the records once, the segment arrays, the
+    per-read offsets into the records (bases, qualities, block_size words)"""
+    n, ns, nb = int(desc.n_reads), int(desc.n_segs), int(raw.raw_bytes)
+
+    def up(ptr, dtype, count, as_dtype=None):
+        if not count:
+            return torch.zeros(1, dtype=torch.from_numpy(np.zeros(1, as_dtype or dtype)).dtype, device=dev)[:0]
+        a = _host_view(ptr, dtype, count)
+        return torch.from_numpy(a.view(as_dtype) if as_dtype is not None else a).to(dev, non_blocking=True)
+
+    t_raw = up(raw.raw, np.uint8, nb) if nb else torch.zeros(16, dtype=torch.uint8, device=dev)
+    coff = _host_view(desc.seg_cigar_off, np.uint32, ns + 1)
+    n_ops = int(coff[-1]) if ns else 0
+    b = DeviceBatch(read_is_reverse=up(desc.read_is_reverse, np.uint8, n), read_seq_len=up(desc.read_seq_len, np.uint32, n, np.int32),
+                    read_seq_off=up(desc.read_seq_off, np.uint64, n, np.int64), seq=t_raw[:nb], seq_fmt=int(desc.seq_fmt),
+                    seg_read=up(desc.seg_read, np.uint32, ns, np.int32), seg_contig=up(desc.seg_contig, np.uint32, ns, np.int32),
+                    seg_pos=up(desc.seg_pos, np.int64, ns), seg_is_fwd_strand=up(desc.seg_is_fwd_strand, np.uint8, ns),
+                    seg_cigar_off=up(desc.seg_cigar_off, np.uint32, ns + 1, np.int32), cigar=up(desc.cigar, np.uint32, n_ops, np.int32))
+    return UploadedRawWindow(t_raw, nb, b, up(fin.read_flags, np.uint16, n, np.int16), up(fin.read_qual_off, np.uint64, n, np.int64),
+                             up(raw.read_rec_off, np.uint64, n, np.int64))
+
+
+def contig_labels(names, dev):
+    """the PS:Z labels (the @SQ names of the read->contig BAM) as device arrays, as sa_inputs carries the reference's: (n, offsets, blob)"""
+    sa, keep = sa_inputs(names, dev)
+    return int(sa.n_chroms), keep["off"], keep["blob"]
+
+
+class PinnedPool:
+    """page-locked blocks for the record bytes of the windows in flight between a lift worker and the writers: a window's block goes back
+    when its bytes are written (DeviceRecords.release), so a handful of blocks serve the whole run"""
+
+    def __init__(self):
+        import threading
+
+        self.free = []
+        self.lock = threading.Lock()
+
+    def take(self, nbytes: int) -> torch.Tensor:
+        with self.lock:
+            for k, t in enumerate(self.free):
+                if t.numel() >= nbytes:
+                    return self.free.pop(k)
+            if self.free:  # outgrown: drop the smallest
+                self.free.sort(key=lambda t: t.numel())
+                self.free.pop(0)
+        return torch.empty(max(nbytes + nbytes // 4, 1 << 20), dtype=torch.uint8, pin_memory=True)
+
+    def give(self, t: torch.Tensor):
+        with self.lock:
+            self.free.append(t)
+
+
+class DeviceRecords:
+    """host copy of a plo_records_out: what the writer takes (`bytes`, `n_bytes`) and the counts, as bam.PloRecordBuf has them"""
+
+    def __init__(self, ro: abi.PloRecordsOut, pool: Optional[PinnedPool] = None, dev=None, with_offsets: bool = False):
+        from .gather import device_view
+
+        self.n_bytes, self.n_records = int(ro.n_bytes), int(ro.n_records)
+        self.n_lifted, self.n_unmapped_copies = int(ro.n_lifted), int(ro.n_unmapped_copies)
+        self.records_ms = float(ro.records_ms)
+        self._pool = pool
+        import time
+
+        nb = max(16, self.n_bytes)
+        t0 = time.perf_counter()
+        self._block = pool.take(nb) if pool is not None else torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+        t1 = time.perf_counter()
+        self.record_off = None
+        if self.n_bytes:
+            self._block[:self.n_bytes].copy_(device_view(ro.bytes, self.n_bytes, torch.uint8, dev), non_blocking=True)  # ONE copy, on the current stream
+        if with_offsets:
+            off = torch.empty((self.n_records + 1) * 8, dtype=torch.uint8, pin_memory=True)
+            off.copy_(device_view(ro.record_off, (self.n_records + 1) * 8, torch.uint8, dev), non_blocking=True)
+            self.record_off = off.numpy().view(np.uint64)
+        torch.cuda.current_stream().synchronize()
+        self.block_s, self.copy_s = t1 - t0, time.perf_counter() - t1  # the page-locked block (a fresh one is an allocation) / the copy
+        self.bytes = self._block.data_ptr()
+
+    def data(self) -> bytes:
+        return self._block[:self.n_bytes].numpy().tobytes()
+
+    def release(self):
+        if self._pool is not None and self._block is not None:
+            self._pool.give(self._block)
+        self._block = None

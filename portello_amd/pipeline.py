@@ -63,6 +63,7 @@ class PipelineStats:
     build_s: float = 0.0     # plo_records_build, summed over workers
     write_s: float = 0.0     # BGZF output (writer thread busy time)
     device_ms: float = 0.0   # HIP-event time of the lift calls
+    records_device_ms: float = 0.0  # device_records: HIP-event time of plo_records_build_dev (plan, scan, emit); build_s then holds only the host time left
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -76,8 +77,12 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    cmdline: str = "", sparse_margin: Optional[int] = 32, device_inflate: Optional[bool] = True,
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
-                   out_shards: int = 1, n_readers: int = 1) -> PipelineStats:  # noqa: E501
-    """device_finish: the records are finished on the device -- the window's batch goes up with all its bases and qualities
+                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False) -> PipelineStats:  # noqa: E501
+    """device_records (default off; implies device_finish): the output records are assembled on the device too -- the window's records
+    go up ONCE as they stand (bam.Window.batch_raw: bases and qualities are views into them), lift -> compact -> finish -> SA ->
+    plo_records_build_dev run on the worker's stream, ONE copy brings the record bytes down and the writer takes them: the host touches
+    no record byte between the reader and plo_bam_write.  Same bytes as the other two modes (tests/test_records_dev.py).
+    device_finish: the records are finished on the device -- the window's batch goes up with all its bases and qualities
     (sparse_margin is ignored), plo_finish_batch_dev (flags, bin, primary record, reverse_alignment_seq_and_qual) and
     plo_sa_segments_dev (SA text) run behind the lift kernels, their results come back and plo_records_build_finished only copies
     them into place.  Same bytes as the host finishing (tests/test_bam.py).
@@ -99,6 +104,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    device_finish = bool(device_finish or device_records)
     half = max(2, io_threads // 2)
     read_threads = read_threads or half
     build_threads = build_threads or half
@@ -188,6 +194,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 t = time.perf_counter()
                 if not win.n_records:
                     desc = None
+                elif device_records:
+                    desc = win.batch_raw()  # (plo_batch_in, plo_finish_in, plo_window_raw): nothing gathered, views into the records
                 elif device_finish:
                     desc = win.batch_desc(with_finish=True)  # (plo_batch_in, plo_finish_in), dense bases
                 else:
@@ -223,7 +231,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 tstream = torch.cuda.Stream(device=dev)  # uploads, kernels and downloads of this worker, in order
                 eng = api.Engine(index, stream=tstream.cuda_stream)
                 sa_in, _sa_keep = devbatch.sa_inputs(ref_names, dev)
-                arena = devbatch.PinnedArena() if not os.environ.get("PLO_PIPELINE_PAGEABLE_RESULTS") else None
+                arena = devbatch.PinnedArena() if not os.environ.get("PLO_PIPELINE_PAGEABLE_RESULTS") and not device_records else None
+                if device_records:
+                    labels = devbatch.contig_labels(contig_names, dev)
+                    pool = devbatch.PinnedPool()
             else:
                 eng = api.Engine(index)
             while True:
@@ -234,7 +245,34 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 rb = None
                 if desc is not None:
                     t = time.perf_counter()
-                    if device_finish:
+                    if device_records:
+                        marks = [("start", t)]
+                        with torch.cuda.stream(tstream):
+                            up = devbatch.upload_raw_window(desc[0], desc[1], desc[2], dev)
+                            marks.append(("upload (issue)", time.perf_counter()))
+                            ddesc = up.batch.desc()
+                            out = eng.liftover_batch_dev(ddesc)
+                            marks.append(("liftover", time.perf_counter()))
+                            eng.compact_output_dev(out)
+                            marks.append(("compact", time.perf_counter()))
+                            fo = eng.finish_batch_dev(ddesc, up.finish_in())
+                            marks.append(("finish", time.perf_counter()))
+                            so = eng.sa_segments_dev(sa_in)
+                            marks.append(("sa text", time.perf_counter()))
+                            ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
+                            marks.append(("records", time.perf_counter()))
+                            rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev)
+                            now = time.perf_counter()
+                            marks.append(("download: page-locked block", now - rb.copy_s))
+                            marks.append(("download: copy", now))
+                        t1 = time.perf_counter()
+                        with lock:
+                            for (_, a), (name, b) in zip(marks, marks[1:]):
+                                st.lift_detail_s[name] = st.lift_detail_s.get(name, 0.0) + (b - a)
+                            st.finish_device_ms += float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms)
+                            st.records_device_ms += rb.records_ms
+                        del up
+                    elif device_finish:
                         marks = [("start", t)]
                         with torch.cuda.stream(tstream):
                             up = devbatch.upload_window(desc[0], desc[1], dev)
@@ -313,6 +351,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                         st.unmapped_passed_through += nu
                         if un is not None:
                             un.write(ub)
+                if rb is not None and hasattr(rb, "release"):
+                    rb.release()  # (device_records: the page-locked block of the window's bytes goes back to its worker's pool)
                 win.close()
                 with lock:
                     st.write_s += time.perf_counter() - t
