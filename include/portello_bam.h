@@ -176,7 +176,15 @@ void plo_bam_free_text(char *text);
 plo_status plo_bam_writer_open(const char *path, const char *header_text, uint32_t n_ref, const char *const *ref_names,
                                const uint32_t *ref_lens, int level, int n_threads, plo_bam_writer **out);
 plo_status plo_bam_write(plo_bam_writer *w, const uint8_t *record_bytes, uint64_t n_bytes);
+/* Appends finished BGZF blocks (plo_bgzf_compress_dev's, downloaded) to the writer as they are: no CRC pass, no deflate, only writes --
+   positional ones from several threads on a seekable file, in order otherwise.  An open partial block of earlier plo_bam_write calls
+   goes out first as a short block of its own, so the order of the records in the stream is kept.  Before anything is written the run
+   is walked block by block (gzip magic, `BC` subfield, BSIZE) and must end exactly at n_bytes: anything else is PLO_ERR_INVALID_ARG
+   and leaves the file untouched.  The run carries no EOF block: plo_bam_writer_close writes it. */
+plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blocks, uint64_t n_bytes);
 plo_status plo_bam_writer_close(plo_bam_writer *w);
+/* bytes the writer has put into its file so far (header blocks included, an open partial block not) */
+uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Phase 1: the contig->reference index from the assembly->reference BAM (scan_contig_bam,

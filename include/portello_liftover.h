@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 7 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw */
+#define PLO_API_VERSION 8 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -378,6 +378,33 @@ typedef struct plo_records_out {
 } plo_records_out;
 
 plo_status plo_records_build_dev(plo_ctx *ctx, const plo_batch_in *in, const plo_records_in *rin, plo_records_out *out);
+
+/* ---- BGZF blocks (device-resident) ------------------------------------------------------------------------------
+ * Cuts the n_bytes at `bytes` -- any device buffer, typically plo_records_out::bytes -- into payloads of 0xff00 bytes (htslib's
+ * BGZF_BLOCK_SIZE), the last one short, and writes each as a complete BGZF block: the 18-byte gzip header with the `BC` subfield and
+ * BSIZE, deflate data ending in a BFINAL block, CRC-32, ISIZE.  One wavefront per block (deflate.hpp).
+ *   level 0: a stored block; the bytes are exactly those plo_bam_write writes for the same payload at level 0.
+ *   level 1: LZ77 within the block and a dynamic Huffman code; a block whose deflate form is not smaller than 5 + len bytes is written
+ *            stored, so level 1 is never larger than level 0 and no block exceeds 18 + 5 + 0xff00 + 8 bytes.  The bytes of a block depend
+ *            on its payload alone.  This is the device's one deflate level; it is not byte-identical with zlib or htslib at any level.
+ *   any other level: PLO_ERR_INVALID_ARG.  n_bytes == 0: PLO_OK with zero blocks.  bytes == NULL with n_bytes > 0: PLO_ERR_INVALID_ARG.
+ * The blocks are packed densely, without the EOF block: plo_bam_write_blocks (portello_bam.h) appends them to a writer as they are.
+ * The call uses buffers of its own: the output of the preceding plo_records_build_dev (and of every other call) on the context stays
+ * valid and unchanged.  Like its neighbours the call returns when its kernels are through.  All pointers are device pointers; outputs
+ * are owned by the context, valid until its next plo_bgzf_compress_dev.
+ * Device memory the context keeps for it (grown to the largest call, freed with the context): the fixed-stride slots and the dense
+ * output, each n_blocks x (18 + 5 + 0xff00 + 8) bytes, i.e. two buffers of about the input's size each (2.4 GB for a 1.19 GB window),
+ * plus, at level 1, 130 560 bytes of token buffer per resident wave (at most 3 workgroups of 4 waves per CU: 401 MB on 256 CUs). */
+typedef struct plo_bgzf_out {
+    const uint8_t *blocks;      /* n_blocks complete BGZF blocks, densely packed, no EOF block                          */
+    uint64_t n_bytes;
+    uint32_t n_blocks;
+    const uint64_t *block_off;  /* [n_blocks + 1]                                                                        */
+    uint64_t n_in;              /* payload bytes consumed                                                                */
+    float bgzf_ms;              /* HIP-event time of this call's kernels                                                 */
+} plo_bgzf_out;
+
+plo_status plo_bgzf_compress_dev(plo_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int level, plo_bgzf_out *out);
 
 /* (plo_finish_batch_dev returns PLO_ERR_DATA when an item of the batch ended LEN_MISMATCH or PANIC -- the reference aborts
    there, :207-229 -- and leaves is_target_region handling (:318-320: no unmapped copy) to the caller.)

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 7  # include/portello_liftover.h
+PLO_API_VERSION = 8  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -181,6 +181,10 @@ class PloRecordsIn(C.Structure):
 class PloRecordsOut(C.Structure):
     _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("n_lifted", C.c_uint32),
                 ("n_unmapped_copies", C.c_uint32), ("records_ms", C.c_float)]
+
+
+class PloBgzfOut(C.Structure):
+    _fields_ = [("blocks", _u8p), ("n_bytes", C.c_uint64), ("n_blocks", C.c_uint32), ("block_off", _u64p), ("n_in", C.c_uint64), ("bgzf_ms", C.c_float)]
 
 
 class PloWindowRaw(C.Structure):  # include/portello_bam.h

@@ -78,6 +78,8 @@ def load_library(path: Optional[str] = None):
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
+    L.plo_bgzf_compress_dev.restype = C.c_int
+    L.plo_bgzf_compress_dev.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(abi.PloBgzfOut)]
     L.plo_ctx_sync.restype = C.c_int
     L.plo_ctx_sync.argtypes = [vp]
     L.plo_ctx_download.restype = C.c_int
@@ -226,6 +228,15 @@ class Engine:
         (plo_records_build_dev); device pointers in and out."""
         out = abi.PloRecordsOut()
         self._check(self.lib.plo_records_build_dev(self.handle, C.byref(desc), C.byref(rin), C.byref(out)), "plo_records_build_dev")
+        return out
+
+    def bgzf_compress_dev(self, dev_bytes, n_bytes: int, level: int) -> abi.PloBgzfOut:
+        """`n_bytes` at the device pointer `dev_bytes` (typically a plo_records_out's bytes) as finished BGZF blocks of 0xff00-byte payloads
+        (plo_bgzf_compress_dev): level 0 stored, level 1 the device's deflate.  Device pointers out; the preceding records_build_dev
+        output stays valid."""
+        out = abi.PloBgzfOut()
+        addr = dev_bytes if isinstance(dev_bytes, int) or dev_bytes is None else C.cast(dev_bytes, C.c_void_p).value
+        self._check(self.lib.plo_bgzf_compress_dev(self.handle, C.c_void_p(addr), int(n_bytes), int(level), C.byref(out)), "plo_bgzf_compress_dev")
         return out
 
     def download(self, dev_ptr, dtype, count: int) -> np.ndarray:

@@ -82,6 +82,10 @@ def lib():
                                           C.POINTER(vp)]
         L.plo_bam_write.restype = C.c_int
         L.plo_bam_write.argtypes = [vp, C.c_void_p, C.c_uint64]
+        L.plo_bam_write_blocks.restype = C.c_int
+        L.plo_bam_write_blocks.argtypes = [vp, C.c_void_p, C.c_uint64]
+        L.plo_bam_writer_file_bytes.restype = C.c_uint64
+        L.plo_bam_writer_file_bytes.argtypes = [vp]
         L.plo_bam_writer_close.restype = C.c_int
         L.plo_bam_writer_close.argtypes = [vp]
         L.plo_bam_last_error.restype = C.c_char_p
@@ -295,6 +299,21 @@ class BamWriter:
             _check(lib().plo_bam_write(self.handle, a.ctypes.data_as(C.c_void_p), a.nbytes), "plo_bam_write")
         else:  # (pointer, n_bytes)
             _check(lib().plo_bam_write(self.handle, C.cast(data[0], C.c_void_p), int(data[1])), "plo_bam_write")
+
+    def write_blocks(self, data):
+        """finished BGZF blocks (api.Engine.bgzf_compress_dev's, downloaded) as they are: bytes, a uint8 array or (pointer, n_bytes);
+        a malformed run is refused (PLO_ERR_INVALID_ARG) before anything is written"""
+        if isinstance(data, (bytes, bytearray)):
+            _check(lib().plo_bam_write_blocks(self.handle, bytes(data), len(data)), "plo_bam_write_blocks")
+        elif isinstance(data, np.ndarray):
+            a = np.ascontiguousarray(data, dtype=np.uint8)
+            _check(lib().plo_bam_write_blocks(self.handle, a.ctypes.data_as(C.c_void_p), a.nbytes), "plo_bam_write_blocks")
+        else:
+            _check(lib().plo_bam_write_blocks(self.handle, C.cast(data[0], C.c_void_p), int(data[1])), "plo_bam_write_blocks")
+
+    def file_bytes(self) -> int:
+        """bytes put into the file so far (an open partial block not counted)"""
+        return int(lib().plo_bam_writer_file_bytes(self.handle)) if self.handle else 0
 
     def close(self):
         if self.handle:

@@ -1415,6 +1415,65 @@ extern "C" plo_status plo_bam_write(plo_bam_writer *w, const uint8_t *bytes, uin
     return w->put(bytes, (size_t)n);
 }
 
+extern "C" plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blocks, uint64_t n) {
+    if (!w || (n && !blocks)) return PLO_ERR_INVALID_ARG;
+    // the run, block by block: nothing is written unless it is well formed from end to end
+    std::vector<uint64_t> cut;  // starts of the pieces the writers take (a few MB each, at block boundaries)
+    const uint64_t piece = (uint64_t)4 << 20;
+    uint64_t at = 0;
+    while (at < n) {
+        static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+        if (n - at < 18 + 2 + 8 || memcmp(blocks + at, hdr, 4) != 0 || memcmp(blocks + at + 10, hdr + 10, 6) != 0)
+            return fail(PLO_ERR_INVALID_ARG, "plo_bam_write_blocks: not a BGZF block at offset " + std::to_string(at));
+        const uint64_t bs = (uint64_t)(blocks[at + 16] | (blocks[at + 17] << 8)) + 1;
+        if (bs < 18 + 2 + 8 || bs > n - at) return fail(PLO_ERR_INVALID_ARG, "plo_bam_write_blocks: the block at offset " + std::to_string(at) + " runs past the end");
+        if (cut.empty() || at - cut.back() >= piece) cut.push_back(at);
+        at += bs;
+    }
+    if (!n) return PLO_OK;
+    if (!w->pend.empty()) {  // the records written before these blocks come before them in the stream
+        plo_status st = w->emit(w->pend.data(), w->pend.size());
+        w->pend.clear();
+        if (st != PLO_OK) return st;
+    }
+    w->reserve(w->file_off + n);
+    cut.push_back(n);
+    if (w->seekable) {
+        std::atomic<int> bad{0};
+        parallel_for(cut.size() - 1, std::min(w->threads, 16), [&](size_t g) {
+            const uint8_t *p = blocks + cut[g];
+            size_t left = (size_t)(cut[g + 1] - cut[g]);
+            uint64_t off = w->file_off + cut[g];
+            while (left) {
+                ssize_t k = pwrite(w->fd, p, left, (off_t)off);
+                if (k < 0 && errno == EINTR) continue;
+                if (k <= 0) {
+                    bad = 1;
+                    return;
+                }
+                p += k;
+                off += (uint64_t)k;
+                left -= (size_t)k;
+            }
+        });
+        if (bad) return fail(PLO_ERR_IO, "write failed");
+    } else {
+        const uint8_t *p = blocks;
+        size_t left = (size_t)n;
+        while (left) {
+            ssize_t k = ::write(w->fd, p, left);
+            if (k < 0 && errno == EINTR) continue;
+            if (k <= 0) return fail(PLO_ERR_IO, "write failed");
+            p += k;
+            left -= (size_t)k;
+        }
+    }
+    w->file_off += n;
+    return PLO_OK;
+}
+
+extern "C" uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w) { return w ? w->file_off : 0; }
+
 extern "C" plo_status plo_bam_writer_close(plo_bam_writer *w) {
     if (!w) return PLO_ERR_INVALID_ARG;
     plo_status st = w->pend.empty() ? PLO_OK : w->emit(w->pend.data(), w->pend.size());

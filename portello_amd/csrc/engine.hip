@@ -42,6 +42,7 @@
 #include "records_core.hpp"
 #include "index_pack.hpp"
 #include "inflate.hpp"
+#include "deflate.hpp"
 #include "lift_core.hpp"
 #include "lane_core.hpp"
 #include "lane_stream.hpp"
@@ -1377,6 +1378,49 @@ __global__ __launch_bounds__(INF_WAVES * 64) void k_bgzf_crc(const uint8_t *out,
     }
 }
 
+// ---- BGZF deflate (deflate.hpp): the output records of a window as finished BGZF blocks, one wave per block ----------------------
+struct DefWave {  // what the encoder needs beyond plo_wave.hpp
+    PLO_DEV void gsync() const {  // LDS and the wave's own global stores (its tokens) are ordered for all its lanes
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // a token this wave stored earlier: read at device scope (L2), the buffer is reused from block to block
+    PLO_DEV uint32_t load_written(const uint16_t *p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+// Four waves per workgroup, each on its own block with its own 10.8 KB of LDS (as k_bgzf_inflate: the waves of a workgroup sit on the
+// four SIMDs of the CU): 44.2 KB per workgroup, three workgroups = twelve blocks in flight per CU.  Persistent: the waves stride over the
+// blocks, so the token buffers are sized by the grid, not by the number of blocks.  size[b] = bytes of block b in its slot (0 on an error).
+constexpr int DEF_WAVES = 4;
+__global__ __launch_bounds__(DEF_WAVES * 64) void k_bgzf_deflate(const uint8_t *in, unsigned long long n_bytes, uint32_t n, int level, uint8_t *slots,
+                                                                 unsigned long long *size, uint16_t *tokens, unsigned *err) {
+    __shared__ DefWork ws_all[DEF_WAVES];
+    __shared__ uint32_t tab[256];
+    tab[threadIdx.x & 255u] = crc32_table_entry(threadIdx.x & 255u);
+    __syncthreads();
+    DefWork &ws = ws_all[wv::wave_id()];
+    const uint32_t wave = blockIdx.x * DEF_WAVES + (uint32_t)wv::wave_id();
+    uint16_t *tok = tokens + (size_t)wave * DEF_TOK_UNITS;
+    DefWave prim;
+    for (uint32_t b = wave; b < n; b += gridDim.x * DEF_WAVES) {
+        const unsigned long long at = (unsigned long long)b * DEF_MAX_IN;
+        const uint32_t len = (uint32_t)(n_bytes - at < DEF_MAX_IN ? n_bytes - at : DEF_MAX_IN);
+        uint32_t sz = 0;
+        const int rc = bgzf_deflate_block(prim, ws, tab, in + at, len, slots + (size_t)b * DEF_SLOT, DEF_SLOT, level, tok, &sz);
+        if (wv::lane() == 0) {
+            size[b] = rc == DEF_OK ? sz : 0;
+            if (rc != DEF_OK) wv::atomic_add_global(err, 1u);
+        }
+        prim.gsync();
+    }
+}
+// the slots' blocks side by side: a workgroup per block at a time, 16-byte stores (copy_span, records_core.hpp)
+__global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, const unsigned long long *off, uint32_t n, uint8_t *dense) {
+    for (uint32_t b = blockIdx.x; b < n; b += gridDim.x)
+        copy_span<true>(dense + off[b], slots + (size_t)b * DEF_SLOT, off[b + 1] - off[b], (int)threadIdx.x, (int)blockDim.x);
+}
+
 // ---- self-test of the wave primitives (plo_selftest) -------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_selftest(const int *in, int *out) {
     int lane = wv::lane();
@@ -1483,7 +1527,9 @@ struct plo_ctx {
     // workspace
     DevBuf f_flag, f_bin, f_end, f_prim, f_isoff, f_iqoff, f_iread, f_nl, f_pitem, f_uflag, f_rsoff, f_rqoff, f_su, f_qu, f_soff,
         f_qoff, f_rseq, f_rqual, f_fflag, f_frank, f_flist, sa_len, sa_off, sa_text, r_plan, r_size, r_start, r_partial, r_recoff, r_out, r_err;
-    HostBuf h_rec;
+    DevBuf z_slots, z_size, z_off, z_partial, z_tok, z_out, z_err;  // plo_bgzf_compress_dev: buffers of its own
+    HostBuf h_rec, h_bgzf;
+    hipEvent_t zev[2] = {nullptr, nullptr};
     DevWork last_wk{};
     DevBatch last_bt{};
     bool have_last = false, have_finish = false, have_sa = false;
@@ -1839,7 +1885,7 @@ void plo_ctx_destroy(plo_ctx *c) {
     (void)hipSetDevice(c->ix->device);
     (void)hipStreamSynchronize(c->stream);
     DevBuf *bufs[] = {&c->f_flag, &c->f_bin, &c->f_end, &c->f_prim, &c->f_isoff, &c->f_iqoff, &c->f_iread, &c->f_nl, &c->f_pitem,
-                      &c->f_uflag, &c->f_rsoff, &c->f_rqoff, &c->f_su, &c->f_qu, &c->f_soff, &c->f_qoff, &c->f_rseq, &c->f_rqual, &c->f_fflag, &c->f_frank, &c->f_flist, &c->sa_len, &c->sa_off, &c->sa_text, &c->r_plan, &c->r_size, &c->r_start, &c->r_partial, &c->r_recoff, &c->r_out, &c->r_err,
+                      &c->f_uflag, &c->f_rsoff, &c->f_rqoff, &c->f_su, &c->f_qu, &c->f_soff, &c->f_qoff, &c->f_rseq, &c->f_rqual, &c->f_fflag, &c->f_frank, &c->f_flist, &c->sa_len, &c->sa_off, &c->sa_text, &c->r_plan, &c->r_size, &c->r_start, &c->r_partial, &c->r_recoff, &c->r_out, &c->r_err, &c->z_slots, &c->z_size, &c->z_off, &c->z_partial, &c->z_tok, &c->z_out, &c->z_err,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1849,7 +1895,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1857,6 +1903,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->fev[i]) (void)hipEventDestroy(c->fev[i]);
     for (int i = 0; i < 4; ++i)
         if (c->rev[i]) (void)hipEventDestroy(c->rev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->zev[i]) (void)hipEventDestroy(c->zev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -3176,6 +3224,79 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     out->record_off = d.record_off;
     out->n_unmapped_copies = (uint32_t)h[2];
     out->n_lifted = (uint32_t)(n_rec - h[2]);
+    return PLO_OK;
+}
+
+// The n_bytes at `bytes` as BGZF blocks (deflate.hpp): k_bgzf_deflate into fixed-stride slots, the 64-bit scan of the blocks' sizes,
+// k_bgzf_pack.  One wait, behind the pack: the dense buffer is sized for stored blocks, so no size has to come back first.
+plo_status plo_bgzf_compress_dev(plo_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int level, plo_bgzf_out *out) {
+    if (!c || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    c->err.clear();
+    if (level != 0 && level != 1) {
+        c->err = "plo_bgzf_compress_dev: level " + std::to_string(level) + ": the device writes stored blocks (0) or its one deflate level (1)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (n_bytes && !bytes) {
+        c->err = "plo_bgzf_compress_dev: no bytes";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const uint64_t nblk64 = (n_bytes + DEF_MAX_IN - 1) / DEF_MAX_IN;
+    if (nblk64 > 0x7fffffffull) {
+        c->err = "plo_bgzf_compress_dev: more than 2^31 blocks in one call";
+        return PLO_ERR_RANGE;
+    }
+    const uint32_t n = (uint32_t)nblk64;
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->zev[i]) HIP_TRY(c, hipEventCreate(&c->zev[i]));
+    HIP_TRY(c, c->z_off.ensure(((size_t)n + 1) * 8));
+    HIP_TRY(c, c->h_bgzf.ensure(64));
+    unsigned long long *h = c->h_bgzf.as<unsigned long long>();
+    memset(h, 0, 64);
+    out->block_off = c->z_off.as<uint64_t>();
+    if (!n) {
+        HIP_TRY(c, hipMemsetAsync(c->z_off.p, 0, 8, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        HIP_TRY(c, c->z_out.ensure(16));
+        out->blocks = c->z_out.as<uint8_t>();
+        return PLO_OK;
+    }
+    // resident workgroups: three per CU by LDS (sizeof(DefWork) x 4 + 1 KB each)
+    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, (160u << 10) / (sizeof(DefWork) * DEF_WAVES + 1024));
+    const uint32_t grid = std::min<uint32_t>((n + DEF_WAVES - 1) / DEF_WAVES, (uint32_t)std::max(1, c->n_cus) * per_cu);
+    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    HIP_TRY(c, c->z_slots.ensure((size_t)n * DEF_SLOT));
+    HIP_TRY(c, c->z_size.ensure((size_t)n * 8));
+    HIP_TRY(c, c->z_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->z_out.ensure((size_t)n * DEF_MAX_BLOCK + 16));
+    HIP_TRY(c, c->z_err.ensure(16));
+    if (level == 1) HIP_TRY(c, c->z_tok.ensure((size_t)grid * DEF_WAVES * DEF_TOK_UNITS * 2));
+    unsigned long long *size = c->z_size.as<unsigned long long>(), *off = c->z_off.as<unsigned long long>();
+    HIP_TRY(c, hipMemsetAsync(c->z_err.p, 0, 4, st));
+    HIP_TRY(c, hipEventRecord(c->zev[0], st));
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(DEF_WAVES * 64), 0, st, bytes, (unsigned long long)n_bytes, n, level, c->z_slots.as<uint8_t>(), size,
+                       c->z_tok.as<uint16_t>(), c->z_err.as<unsigned>());
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)size, n, nb, c->z_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->z_partial.as<unsigned long long>(), n, nb, off);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)size, n, nb, (const unsigned long long *)c->z_partial.as<unsigned long long>(), off);
+    hipLaunchKernelGGL(k_bgzf_pack, dim3(std::min<uint32_t>(n, (uint32_t)c->n_cus * 8u)), dim3(256), 0, st, (const uint8_t *)c->z_slots.as<uint8_t>(),
+                       (const unsigned long long *)off, n, c->z_out.as<uint8_t>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->zev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, off + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h + 1, c->z_err.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((unsigned)h[1]) {
+        c->err = "plo_bgzf_compress_dev: " + std::to_string((unsigned)h[1]) + " blocks were refused by the encoder";
+        return PLO_ERR_INTERNAL;
+    }
+    (void)hipEventElapsedTime(&out->bgzf_ms, c->zev[0], c->zev[1]);
+    out->blocks = c->z_out.as<uint8_t>();
+    out->n_bytes = h[0];
+    out->n_blocks = n;
+    out->n_in = n_bytes;
     return PLO_OK;
 }
 

@@ -415,3 +415,37 @@ class DeviceRecords:
         if self._pool is not None and self._block is not None:
             self._pool.give(self._block)
         self._block = None
+
+
+class DeviceBlocks:
+    """the records of a plo_records_out compressed on the device (api.Engine.bgzf_compress_dev) and brought down as finished BGZF blocks:
+    what bam.BamWriter.write_blocks takes (`bytes`, `n_bytes`), the counts of the records as DeviceRecords has them, `n_in` = the record
+    bytes the blocks hold.  The record bytes themselves never leave the device."""
+    is_blocks = True
+
+    def __init__(self, eng, ro: abi.PloRecordsOut, level: int, pool: Optional[PinnedPool] = None, dev=None):
+        from .gather import device_view
+        import time
+
+        self.n_records, self.n_lifted, self.n_unmapped_copies = int(ro.n_records), int(ro.n_lifted), int(ro.n_unmapped_copies)
+        self.records_ms = float(ro.records_ms)
+        bo = eng.bgzf_compress_dev(ro.bytes, int(ro.n_bytes), level)
+        self.n_in, self.n_bytes, self.n_blocks, self.bgzf_ms = int(bo.n_in), int(bo.n_bytes), int(bo.n_blocks), float(bo.bgzf_ms)
+        self._pool = pool
+        nb = max(16, self.n_bytes)
+        t0 = time.perf_counter()
+        self._block = pool.take(nb) if pool is not None else torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+        t1 = time.perf_counter()
+        if self.n_bytes:
+            self._block[:self.n_bytes].copy_(device_view(bo.blocks, self.n_bytes, torch.uint8, dev), non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.block_s, self.copy_s = t1 - t0, time.perf_counter() - t1
+        self.bytes = self._block.data_ptr()
+
+    def data(self) -> bytes:
+        return self._block[:self.n_bytes].numpy().tobytes()
+
+    def release(self):
+        if self._pool is not None and self._block is not None:
+            self._pool.give(self._block)
+        self._block = None

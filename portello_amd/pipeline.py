@@ -63,6 +63,8 @@ class PipelineStats:
     build_s: float = 0.0     # plo_records_build, summed over workers
     write_s: float = 0.0     # BGZF output (writer thread busy time)
     device_ms: float = 0.0   # HIP-event time of the lift calls
+    bgzf_device_ms: float = 0.0  # device_bgzf: HIP-event time of plo_bgzf_compress_dev (deflate / stored framing, scan, pack)
+    out_file_bytes: int = 0      # size of the closed output file(s) of the lifted records (header and EOF blocks included)
     records_device_ms: float = 0.0  # device_records: HIP-event time of plo_records_build_dev (plan, scan, emit); build_s then holds only the host time left
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
@@ -77,8 +79,15 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    cmdline: str = "", sparse_margin: Optional[int] = 32, device_inflate: Optional[bool] = True,
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
-                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False) -> PipelineStats:  # noqa: E501
-    """device_records (default off; implies device_finish): the output records are assembled on the device too -- the window's records
+                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False) -> PipelineStats:  # noqa: E501
+    """device_bgzf (default off; needs device_records=True): the window's record bytes are framed as BGZF blocks on the device too
+    (plo_bgzf_compress_dev behind plo_records_build_dev) and only the finished blocks come down; the writer appends them as they are
+    (plo_bam_write_blocks: no CRC pass, no deflate on the host).  `level` then selects between the device's two forms: level == 0 is
+    stored framing, byte for byte the host writer's; level >= 1 is the device's ONE deflate level (LZ77 + dynamic Huffman codes, about
+    zlib level 1) -- levels 2-9 do not exist on the device and mean the same as 1.  Every window ends its last block, as the host writer
+    does only at the end of the file, so a file of several windows has a few more (short) blocks than the host-framed one.  The unmapped
+    pass-through and the unassembled file stay on the host writer at `level`.
+    device_records (default off; implies device_finish): the output records are assembled on the device too -- the window's records
     go up ONCE as they stand (bam.Window.batch_raw: bases and qualities are views into them), lift -> compact -> finish -> SA ->
     plo_records_build_dev run on the worker's stream, ONE copy brings the record bytes down and the writer takes them: the host touches
     no record byte between the reader and plo_bam_write.  Same bytes as the other two modes (tests/test_records_dev.py).
@@ -104,6 +113,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if device_bgzf and not device_records:
+        raise ValueError("device_bgzf compresses the records plo_records_build_dev leaves on the device: it needs device_records=True")
     device_finish = bool(device_finish or device_records)
     half = max(2, io_threads // 2)
     read_threads = read_threads or half
@@ -261,7 +272,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             marks.append(("sa text", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
-                            rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev)
+                            if device_bgzf:
+                                rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev)
+                                marks.append(("bgzf", time.perf_counter() - rb.block_s - rb.copy_s))
+                            else:
+                                rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev)
                             now = time.perf_counter()
                             marks.append(("download: page-locked block", now - rb.copy_s))
                             marks.append(("download: copy", now))
@@ -271,6 +286,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 st.lift_detail_s[name] = st.lift_detail_s.get(name, 0.0) + (b - a)
                             st.finish_device_ms += float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms)
                             st.records_device_ms += rb.records_ms
+                            st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up
                     elif device_finish:
                         marks = [("start", t)]
@@ -313,7 +329,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                         st.records_out += int(rb.n_records)
                         st.lifted += int(rb.n_lifted)
                         st.unmapped_copies += int(rb.n_unmapped_copies)
-                        st.bytes_out += int(rb.n_bytes)
+                        st.bytes_out += int(getattr(rb, "n_in", rb.n_bytes))
                 put(q_out, (win, rb))
         except BaseException as e:  # noqa: BLE001
             st.errors.append(f"lift worker {k}: {e!r}")
@@ -344,7 +360,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 win, rb = item
                 t = time.perf_counter()
                 if rb is not None and rb.n_bytes:
-                    wrs[k].write((rb.bytes, rb.n_bytes))
+                    if getattr(rb, "is_blocks", False):
+                        wrs[k].write_blocks((rb.bytes, rb.n_bytes))
+                    else:
+                        wrs[k].write((rb.bytes, rb.n_bytes))
                 ub, nu = win.unmapped_bytes()
                 if nu:
                     with un_lock:
@@ -375,6 +394,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         t.join()
     for wr in wrs:
         wr.close()
+    st.out_file_bytes = sum(os.path.getsize(p_) for p_ in out_paths if os.path.exists(p_))
     st.stage_done_s["output closed"] = time.perf_counter() - t0
     if un is not None:
         un.close()

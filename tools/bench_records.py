@@ -5,9 +5,14 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_records_build_dev: records_ms (HIP events), bytes read + written per records_ms, the D2H time of the record bytes, the H2D time
     of the raw window against the H2D of the separate seq + qual arrays it replaces;
   - the byte-copy instantiation (PLO_RECORDS_BYTECOPY=1, a context of its own) against the 16-byte one.
+  - plo_bgzf_compress_dev on the records where plo_records_build_dev left them (--bgzf-out): bgzf_ms at level 0 and at --level, the
+    compressed bytes and their D2H time beside the D2H of the raw bytes, payload GB/s through the kernels beside the 16-thread host writer
+    at the same level on the same bytes; every block is inflated with zlib and compared.  With --e2e-reads also run_bam_to_bam with the
+    host writer against device_bgzf, at level 0 and at --level, three alternating runs each.
 Exits non-zero on any byte mismatch between the device's records and the host's.
 
     python tools/bench_records.py --reads 50000 --out profiles/r07_records_window.json
+    python tools/bench_records.py --reads 50000 --level 1 --bgzf-out profiles/r08_bgzf_window.json --e2e-reads 180000
 """
 import argparse
 import ctypes as C
@@ -66,6 +71,42 @@ def end_to_end(n_reads):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def end_to_end_bgzf(n_reads, level):
+    """run_bam_to_bam reads/s with device_records=True: the host writer against device_bgzf, at level 0 and at `level`, three alternating runs each"""
+    import shutil
+
+    from portello_amd import api, bamsynth, pipeline, synth
+
+    w = synth.generate(synth.config("chr20", n_reads=n_reads), device="cuda")
+    d = tempfile.mkdtemp(prefix="plo_bgzf_e2e_")
+    try:
+        inp = os.path.join(d, "reads.bam")
+        meta = bamsynth.write_read_bam(w, inp, level=1, n_threads=16)
+        ixd = w.index_data()
+        index = api.Index(w.index_data_device())
+        cn, rn, rl = meta["contig_names"], bamsynth.ref_names(w), [int(s.numel()) for s in w.chrom_seq]
+        kw = dict(window_reads=7500, n_workers=3, io_threads=16, out_shards=4, device_records=True)
+        pipeline.run_bam_to_bam(inp, os.path.join(d, "warm.bam"), index, ixd, cn, rn, rl, window_reads=2000, n_workers=1, device_records=True, device_bgzf=True, level=level)
+        res = {"reads": n_reads, "config": kw, "unit": "reads/s"}
+        for lv in (level, 0):
+            runs = {"host_writer": [], "device_bgzf": []}
+            detail = {}
+            for k in range(3):
+                for mode in ("host_writer", "device_bgzf"):
+                    st = pipeline.run_bam_to_bam(inp, os.path.join(d, f"{mode}_{k}.bam"), index, ixd, cn, rn, rl, level=lv, device_bgzf=mode == "device_bgzf", **kw)
+                    runs[mode].append(st.reads / st.seconds)
+                    detail[mode] = {"seconds": st.seconds, "lift_s": st.lift_s, "write_s": st.write_s, "read_s": st.read_s, "bgzf_device_ms": st.bgzf_device_ms,
+                                    "records_device_ms": st.records_device_ms, "out_file_bytes": st.out_file_bytes, "bytes_out": st.bytes_out,
+                                    "lift_detail_s": dict(st.lift_detail_s)}
+                    for p_ in st.out_paths:
+                        os.unlink(p_)
+            res[f"level_{lv}"] = {**{m: {"median": statistics.median(v), "best": max(v), "runs": v} for m, v in runs.items()}, "last_run_detail": detail}
+        index.close()
+        return res
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -76,6 +117,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--commit", default="", help="commit hash to record (a tree without .git cannot tell)")
     ap.add_argument("--e2e-reads", type=int, default=0, help="> 0: also run_bam_to_bam device_finish against device_records on that many reads, three runs each, alternating")
+    ap.add_argument("--level", type=int, default=1, help="BGZF level of the compress step beside level 0 (the device has one deflate level: 1)")
+    ap.add_argument("--bgzf-out", default="", help="run the compress step (plo_bgzf_compress_dev) and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -134,9 +177,34 @@ def main():
             if k >= a.warmup:
                 ms.append(float(ro.records_ms))
                 d2h.append((time.perf_counter() - t) * 1e3)
+        bgzf = {}
+        if a.bgzf_out and not bytecopy:  # the records stay where plo_records_build_dev left them
+            import zlib
+
+            raw = land[:int(ro.n_bytes)].numpy()
+            for lv in sorted({0, a.level}):
+                zms, zd2h, bland = [], [], None
+                for k in range(a.warmup + a.reps):
+                    bo = eng.bgzf_compress_dev(ro.bytes, int(ro.n_bytes), lv)
+                    if bland is None:
+                        bland = torch.empty(max(16, int(bo.n_bytes)), dtype=torch.uint8, pin_memory=True)
+                    src = device_view(bo.blocks, int(bo.n_bytes), torch.uint8, dev)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    bland[:int(bo.n_bytes)].copy_(src, non_blocking=True)
+                    torch.cuda.synchronize()
+                    if k >= a.warmup:
+                        zms.append(float(bo.bgzf_ms))
+                        zd2h.append((time.perf_counter() - t) * 1e3)
+                off = eng.download(bo.block_off, np.uint64, int(bo.n_blocks) + 1)
+                blk = bland[:int(bo.n_bytes)].numpy()
+                same = all(zlib.decompress(blk[int(off[i]):int(off[i + 1])].tobytes(), 31) == raw[i * 0xff00:(i + 1) * 0xff00].tobytes() for i in range(int(bo.n_blocks)))
+                bgzf[f"level_{lv}"] = {"bgzf_ms": stats(zms), "d2h_blocks_ms": stats(zd2h), "blocks_bytes": int(bo.n_bytes), "n_blocks": int(bo.n_blocks),
+                                      "ratio": int(bo.n_bytes) / max(1, int(ro.n_bytes)), "payload_gbs": int(ro.n_bytes) / (statistics.median(zms) * 1e-3) / 1e9,
+                                      "inflates_to_the_records": bool(same)}
         rec = devbatch.DeviceRecords(ro, dev=dev, with_offsets=True)
         host = devbatch.HostResults(eng, out, fo, so, win.n_records, dev=dev)
-        return dict(eng=eng, up=up, rec=rec, host=host, ms=ms, d2h=d2h, h2d=h2d[a.warmup:], fin_ms=float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms), keep=(keep, labels))
+        return dict(eng=eng, up=up, rec=rec, host=host, ms=ms, d2h=d2h, h2d=h2d[a.warmup:], fin_ms=float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms), keep=(keep, labels), bgzf=bgzf)
 
     vec = device_route(False)
     # the yardstick on the same window and the same lift result (the dense batch of plo_bam_window_batch, as the device_finish mode builds it)
@@ -176,7 +244,34 @@ def main():
     }
     res["device_kernel_plus_d2h_ms"] = res["device_records_ms"]["median"] + res["d2h_record_bytes_ms"]["median"]
     res["device_below_host"] = res["device_kernel_plus_d2h_ms"] < res["host_records_build_finished_ms"]["median"]
-    if a.e2e_reads > 0:
+    if a.bgzf_out:
+        # the 16-thread host writer on the same bytes, BGZF blocks only (a file on the temporary directory's filesystem)
+        hw = {}
+        for lv in sorted({0, a.level}):
+            ts = []
+            for k in range(3):
+                wp = os.path.join(tmp, "host_writer.bam")
+                wr = bam.BamWriter(wp, "@HD\tVN:1.6\n", ["c"], [1], level=lv, n_threads=16)
+                t = time.perf_counter()
+                wr.write(hdata)
+                wr.close()
+                ts.append((time.perf_counter() - t) * 1e3)
+                size = os.path.getsize(wp)
+                os.unlink(wp)
+            hw[f"level_{lv}"] = {"write_ms": stats(ts), "file_bytes": size, "payload_gbs": n_bytes / (statistics.median(ts) * 1e-3) / 1e9, "threads": 16}
+        zres = {"tool": "tools/bench_records.py", "reads": a.reads, "record_bytes": n_bytes, "commit": res["commit"], "source_hash": res["source_hash"], "warmup": a.warmup,
+                "reps": a.reps, "d2h_record_bytes_ms": res["d2h_record_bytes_ms"], "device_records_ms": res["device_records_ms"], "device": vec["bgzf"], "host_writer": hw}
+        ok = ok and all(v["inflates_to_the_records"] for v in vec["bgzf"].values())
+        os.makedirs(os.path.dirname(os.path.abspath(a.bgzf_out)), exist_ok=True)
+        for part in ("window", "end_to_end"):  # the window's figures are on disk before the long runs start
+            if part == "end_to_end":
+                if a.e2e_reads <= 0:
+                    break
+                zres["end_to_end"] = end_to_end_bgzf(a.e2e_reads, a.level)
+            with open(a.bgzf_out, "w") as fh:
+                fh.write(json.dumps(zres, indent=1) + "\n")
+        print(json.dumps(zres))
+    elif a.e2e_reads > 0:
         res["end_to_end"] = end_to_end(a.e2e_reads)
     line = json.dumps(res)
     print(line)
