@@ -124,6 +124,9 @@ typedef struct plo_window_raw {
     const uint64_t *read_rec_off; /* [n_reads] */
 } plo_window_raw;
 plo_status plo_bam_window_batch_raw(plo_bam_window *w, plo_batch_in *batch, plo_finish_in *fin, plo_window_raw *raw);
+/* `raw` alone, WITHOUT building a batch: for the path that builds it on the device from the uploaded records (plo_batch_build_dev).  The
+ * window keeps no batch then (plo_records_build on it is refused as before any plo_bam_window_batch). */
+plo_status plo_bam_window_raw(plo_bam_window *w, plo_window_raw *raw);
 
 /* The same transformation for a batch that already exists with dense PLO_SEQ_BAM4 bases in host memory (seg_read non-decreasing).
  * `out` needs plo_sparse_seq_bound(dense) bytes (page-locked memory from plo_host_alloc makes the upload faster), out_read_off

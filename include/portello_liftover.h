@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 8 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks */
+#define PLO_API_VERSION 9 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -405,6 +405,52 @@ typedef struct plo_bgzf_out {
 } plo_bgzf_out;
 
 plo_status plo_bgzf_compress_dev(plo_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int level, plo_bgzf_out *out);
+
+/* ---- The liftover batch (device-resident) ------------------------------------------------------------------------
+ * Builds the plo_batch_in / plo_finish_in of a window from its records as they stand in device memory: what plo_bam_window_batch_raw
+ * (portello_bam.h) builds on the host, array for array -- the sequencing-order split segments of every primary record
+ * (get_seq_order_read_split_segments, split_read.rs:56-155): the CG:B,I restore of a long CIGAR, the first SA:Z field cut at ';' and ','
+ * with split_terminator's rules (sa_tag_parser.rs:26-59), the clip positions, the stable sort by sequencing-order start, the labels looked
+ * up in the @SQ names given here (a hash table built on the device on every call).  batch.seq = fin.qual = records; read_seq_off /
+ * read_qual_off are byte offsets into it; seq_fmt = PLO_SEQ_BAM4; n_items = 0 (the engine enumerates).
+ * Every record is checked before any of its bytes is trusted: a read_rec_off, block_size, l_qname / n_cigar / l_seq that points outside
+ * `records` -> PLO_ERR_INVALID_ARG.  Input the host batcher refuses -> PLO_ERR_DATA: err_read is the LOWEST failing read, err_kind its
+ * first failure in the host's order (segments in text order; per segment field count, field parse, no aligned op, read size, unknown label;
+ * then an empty split segment), and plo_last_error names both.  More than 2^31 - 1 CIGAR ops in the window -> PLO_ERR_RANGE.  A failing
+ * call leaves nothing the caller may use.  n_reads == 0: PLO_OK with empty arrays.
+ * The stream is waited for once for the totals and the error word, and once behind the emit kernel for the event times.  The call uses
+ * buffers of its own, grown to the largest call and freed with the context: its outputs stay valid across the following lift / compact /
+ * finish / SA / records / bgzf calls on the context, until its next plo_batch_build_dev.  All pointers are device pointers. */
+typedef enum plo_bb_err {
+    PLO_BB_ERR_NONE = 0,
+    PLO_BB_ERR_SA_NOT_Z = 1,       /* the SA aux field is not a string                                        */
+    PLO_BB_ERR_FIELD_COUNT = 2,    /* an SA segment without exactly six fields (an empty one included)        */
+    PLO_BB_ERR_MALFORMED = 3,      /* pos / CIGAR / MAPQ / NM of an SA segment does not parse                 */
+    PLO_BB_ERR_UNALIGNED = 4,      /* an SA segment whose CIGAR has no M, = or X op                           */
+    PLO_BB_ERR_READ_SIZE = 5,      /* an SA segment's read length differs from the primary record's           */
+    PLO_BB_ERR_UNKNOWN_CONTIG = 6, /* an SA segment on a contig the header does not name                      */
+    PLO_BB_ERR_EMPTY_SEGMENT = 7   /* a segment that covers no read base in sequencing order                  */
+} plo_bb_err;
+
+typedef struct plo_batch_build_in {
+    const uint8_t *records;          /* the window's stretch of the BAM stream                                          */
+    uint64_t records_bytes;
+    const uint64_t *read_rec_off;    /* [n_reads] offset of primary record r's block_size word inside `records`         */
+    uint32_t n_reads;
+    uint32_t n_contigs;              /* @SQ names of the read->contig BAM                                               */
+    const uint32_t *contig_name_off; /* [n_contigs + 1] byte offsets into contig_names                                  */
+    const uint8_t *contig_names;     /* concatenated labels, no terminators                                             */
+} plo_batch_build_in;
+
+typedef struct plo_batch_build_out {
+    plo_batch_in batch;  /* device pointers owned by the context; seq = records, seq_fmt = PLO_SEQ_BAM4, n_items = 0 */
+    plo_finish_in fin;   /* qual = records                                                                           */
+    uint32_t err_read;   /* lowest failing read, UINT32_MAX if none                                                  */
+    uint32_t err_kind;   /* PLO_BB_ERR_*                                                                             */
+    float batch_ms;      /* HIP-event time of the call's kernels                                                     */
+} plo_batch_build_out;
+
+plo_status plo_batch_build_dev(plo_ctx *ctx, const plo_batch_build_in *in, plo_batch_build_out *out);
 
 /* (plo_finish_batch_dev returns PLO_ERR_DATA when an item of the batch ended LEN_MISMATCH or PANIC -- the reference aborts
    there, :207-229 -- and leaves is_target_region handling (:318-320: no unmapped copy) to the caller.)

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 8  # include/portello_liftover.h
+PLO_API_VERSION = 9  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -185,6 +185,27 @@ class PloRecordsOut(C.Structure):
 
 class PloBgzfOut(C.Structure):
     _fields_ = [("blocks", _u8p), ("n_bytes", C.c_uint64), ("n_blocks", C.c_uint32), ("block_off", _u64p), ("n_in", C.c_uint64), ("bgzf_ms", C.c_float)]
+
+
+# plo_bb_err: what plo_batch_build_dev found in the lowest failing read
+BB_ERR_NONE = 0
+BB_ERR_SA_NOT_Z = 1
+BB_ERR_FIELD_COUNT = 2
+BB_ERR_MALFORMED = 3
+BB_ERR_UNALIGNED = 4
+BB_ERR_READ_SIZE = 5
+BB_ERR_UNKNOWN_CONTIG = 6
+BB_ERR_EMPTY_SEGMENT = 7
+BB_NO_READ = 0xFFFFFFFF
+
+
+class PloBatchBuildIn(C.Structure):
+    _fields_ = [("records", _u8p), ("records_bytes", C.c_uint64), ("read_rec_off", _u64p), ("n_reads", C.c_uint32), ("n_contigs", C.c_uint32),
+                ("contig_name_off", _u32p), ("contig_names", _u8p)]
+
+
+class PloBatchBuildOut(C.Structure):
+    _fields_ = [("batch", PloBatchIn), ("fin", PloFinishIn), ("err_read", C.c_uint32), ("err_kind", C.c_uint32), ("batch_ms", C.c_float)]
 
 
 class PloWindowRaw(C.Structure):  # include/portello_bam.h

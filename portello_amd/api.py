@@ -78,6 +78,8 @@ def load_library(path: Optional[str] = None):
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
+    L.plo_batch_build_dev.restype = C.c_int
+    L.plo_batch_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchBuildIn), C.POINTER(abi.PloBatchBuildOut)]
     L.plo_bgzf_compress_dev.restype = C.c_int
     L.plo_bgzf_compress_dev.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(abi.PloBgzfOut)]
     L.plo_ctx_sync.restype = C.c_int
@@ -228,6 +230,19 @@ class Engine:
         (plo_records_build_dev); device pointers in and out."""
         out = abi.PloRecordsOut()
         self._check(self.lib.plo_records_build_dev(self.handle, C.byref(desc), C.byref(rin), C.byref(out)), "plo_records_build_dev")
+        return out
+
+    def batch_build_dev(self, bin_: abi.PloBatchBuildIn) -> abi.PloBatchBuildOut:
+        """The window's plo_batch_in / plo_finish_in built on the device from its uploaded records (plo_batch_build_dev); device pointers in
+        and out, the arrays valid until the engine's next batch_build_dev.  A PLO_ERR_DATA failure carries `err_read` (the lowest failing
+        read) and `err_kind` (abi.BB_ERR_*) on the exception."""
+        out = abi.PloBatchBuildOut()
+        st = self.lib.plo_batch_build_dev(self.handle, C.byref(bin_), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_batch_build_dev: {msg.decode() if msg else ''}")
+            e.err_read, e.err_kind = int(out.err_read), int(out.err_kind)
+            raise e
         return out
 
     def bgzf_compress_dev(self, dev_bytes, n_bytes: int, level: int) -> abi.PloBgzfOut:

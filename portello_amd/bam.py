@@ -64,6 +64,8 @@ def lib():
         L.plo_bam_window_batch_sparse.argtypes = [vp, C.c_uint32, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn)]
         L.plo_bam_window_batch_raw.restype = C.c_int
         L.plo_bam_window_batch_raw.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloWindowRaw)]
+        L.plo_bam_window_raw.restype = C.c_int
+        L.plo_bam_window_raw.argtypes = [vp, C.POINTER(abi.PloWindowRaw)]
         L.plo_sparse_seq_bound.restype = C.c_uint64
         L.plo_sparse_seq_bound.argtypes = [C.POINTER(abi.PloBatchIn)]
         L.plo_sparse_seq_pack.restype = C.c_int
@@ -172,6 +174,13 @@ class Window:
         _check(lib().plo_bam_window_batch_raw(self.handle, C.byref(b), C.byref(f), C.byref(r)), "plo_bam_window_batch_raw")
         self._batch = b
         return b, f, r
+
+    def raw(self) -> abi.PloWindowRaw:
+        """the window's stretch of the BAM stream and the offsets of its primary records, WITHOUT building a batch (plo_bam_window_raw): for
+        the route that builds the batch on the device from the uploaded records (api.Engine.batch_build_dev)"""
+        r = abi.PloWindowRaw()
+        _check(lib().plo_bam_window_raw(self.handle, C.byref(r)), "plo_bam_window_raw")
+        return r
 
     def batch_data(self) -> abi.BatchData:
         """numpy copy of the batch (for the oracle / the host-buffer entry point)"""

@@ -518,6 +518,15 @@ extern "C" plo_status plo_bam_window_batch_raw(plo_bam_window *w, plo_batch_in *
     return PLO_OK;
 }
 
+extern "C" plo_status plo_bam_window_raw(plo_bam_window *w, plo_window_raw *raw) {
+    if (!w || !raw) return PLO_ERR_INVALID_ARG;
+    raw->raw = w->raw.data();
+    raw->raw_bytes = w->raw.size();
+    raw->n_reads = w->n_records();
+    raw->read_rec_off = w->rec_at.data();
+    return PLO_OK;
+}
+
 static plo_status window_batch(plo_bam_window *w, plo_batch_in *batch, plo_finish_in *fin, int sparse_margin, const plo_index_desc *ixd) {
     if (!w || !batch) return PLO_ERR_INVALID_ARG;
     memset(batch, 0, sizeof(*batch));

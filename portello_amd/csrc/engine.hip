@@ -40,6 +40,7 @@
 #include "enumerate.hpp"
 #include "finish_core.hpp"
 #include "records_core.hpp"
+#include "batch_core.hpp"
 #include "index_pack.hpp"
 #include "inflate.hpp"
 #include "deflate.hpp"
@@ -1307,6 +1308,23 @@ __global__ __launch_bounds__(256) void k_rec_emit(DevBatch bt, DevWork wk, DevRe
     for (uint32_t r = blockIdx.x; r < bt.n_reads; r += gridDim.x) records_emit_read<VEC>(bt, wk, d, r, (int)threadIdx.x, (int)blockDim.x);
 }
 
+// ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
+// the label table: a thread per contig name
+__global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < d.n_contigs) bb_table_insert(d, c);
+}
+// plan: a wave per read (the SA text is cut 64 bytes per step, a CIGAR text parsed with a lane per op)
+__global__ __launch_bounds__(256) void k_bb_plan(DevBatchBuild d) {
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r < d.n_reads) batch_plan_read(d, r);  // (wave-uniform)
+}
+// emit: a wave per read at a time
+__global__ __launch_bounds__(256) void k_bb_emit(DevBatchBuild d) {
+    const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t r = w; r < d.n_reads; r += nw) batch_emit_read(d, r);
+}
+
 // ---- BGZF inflate (inflate.hpp): every block of a chunk of the BAM stream at once, one wave per block ----------------------
 struct BgzfBlk {
     unsigned long long coff, uoff;  // offsets of the block's deflate data / inflated bytes inside the chunk buffers
@@ -1528,8 +1546,12 @@ struct plo_ctx {
     DevBuf f_flag, f_bin, f_end, f_prim, f_isoff, f_iqoff, f_iread, f_nl, f_pitem, f_uflag, f_rsoff, f_rqoff, f_su, f_qu, f_soff,
         f_qoff, f_rseq, f_rqual, f_fflag, f_frank, f_flist, sa_len, sa_off, sa_text, r_plan, r_size, r_start, r_partial, r_recoff, r_out, r_err;
     DevBuf z_slots, z_size, z_off, z_partial, z_tok, z_out, z_err;  // plo_bgzf_compress_dev: buffers of its own
-    HostBuf h_rec, h_bgzf;
+    // plo_batch_build_dev: buffers of its own (the label table, plan and scans, the segments in text order, the batch's arrays)
+    DevBuf bb_table, bb_plan, bb_size, bb_start, bb_partial, bb_kind, bb_err, bb_tkey, bb_tnops, bb_tctext, bb_tclen, bb_tcontig, bb_tdst, bb_tpos, bb_tfwd,
+        bb_rev, bb_len, bb_soff, bb_qoff, bb_flags, bb_sread, bb_scontig, bb_spos, bb_sfwd, bb_coff, bb_cigar;
+    HostBuf h_rec, h_bgzf, h_bb;
     hipEvent_t zev[2] = {nullptr, nullptr};
+    hipEvent_t bev[4] = {nullptr, nullptr, nullptr, nullptr};
     DevWork last_wk{};
     DevBatch last_bt{};
     bool have_last = false, have_finish = false, have_sa = false;
@@ -1886,6 +1908,9 @@ void plo_ctx_destroy(plo_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     DevBuf *bufs[] = {&c->f_flag, &c->f_bin, &c->f_end, &c->f_prim, &c->f_isoff, &c->f_iqoff, &c->f_iread, &c->f_nl, &c->f_pitem,
                       &c->f_uflag, &c->f_rsoff, &c->f_rqoff, &c->f_su, &c->f_qu, &c->f_soff, &c->f_qoff, &c->f_rseq, &c->f_rqual, &c->f_fflag, &c->f_frank, &c->f_flist, &c->sa_len, &c->sa_off, &c->sa_text, &c->r_plan, &c->r_size, &c->r_start, &c->r_partial, &c->r_recoff, &c->r_out, &c->r_err, &c->z_slots, &c->z_size, &c->z_off, &c->z_partial, &c->z_tok, &c->z_out, &c->z_err,
+                      &c->bb_table, &c->bb_plan, &c->bb_size, &c->bb_start, &c->bb_partial, &c->bb_kind, &c->bb_err, &c->bb_tkey, &c->bb_tnops, &c->bb_tctext, &c->bb_tclen,
+                      &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
+                      &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1895,7 +1920,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1905,6 +1930,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->rev[i]) (void)hipEventDestroy(c->rev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->zev[i]) (void)hipEventDestroy(c->zev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->bev[i]) (void)hipEventDestroy(c->bev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -3297,6 +3324,175 @@ plo_status plo_bgzf_compress_dev(plo_ctx *c, const uint8_t *bytes, uint64_t n_by
     out->n_bytes = h[0];
     out->n_blocks = n;
     out->n_in = n_bytes;
+    return PLO_OK;
+}
+
+// The window's plo_batch_in / plo_finish_in from its records in device memory (batch_core.hpp): k_bb_table, k_bb_plan, the 64-bit scans of
+// the reads' segment and op counts, one wait for the totals and the error word, k_bb_emit.
+plo_status plo_batch_build_dev(plo_ctx *c, const plo_batch_build_in *in, plo_batch_build_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_read = UINT32_MAX;
+    c->err.clear();
+    const uint32_t nr = in->n_reads;
+    if ((nr && (!in->records || !in->read_rec_off)) || !in->contig_name_off || (in->n_contigs && !in->contig_names)) {
+        c->err = "plo_batch_build_in: the records, their offsets and the contig name table are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (nr > 0x7ffffffeu || in->n_contigs > 0x3fffffffu) {
+        c->err = "plo_batch_build_dev: more than 2^31 - 2 reads or 2^30 contigs";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->bev[i]) HIP_TRY(c, hipEventCreate(&c->bev[i]));
+    const uint32_t nb = std::max(1u, (nr + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    const size_t b = std::max(1u, nr);
+    uint32_t slots = 64;
+    while (slots < 2 * in->n_contigs) slots <<= 1;
+    HIP_TRY(c, c->bb_table.ensure((size_t)slots * 4));
+    HIP_TRY(c, c->bb_plan.ensure(b * BB_PLAN_WORDS * 4));
+    HIP_TRY(c, c->bb_size.ensure(2 * b * 8));
+    HIP_TRY(c, c->bb_start.ensure(2 * (b + 1) * 8));
+    HIP_TRY(c, c->bb_partial.ensure(2 * (size_t)nb * 8));
+    HIP_TRY(c, c->bb_kind.ensure(b * 4));
+    HIP_TRY(c, c->bb_err.ensure(BB_ERR_WORDS * 4));
+    HIP_TRY(c, c->bb_rev.ensure(b));
+    HIP_TRY(c, c->bb_len.ensure(b * 4));
+    HIP_TRY(c, c->bb_soff.ensure(b * 8));
+    HIP_TRY(c, c->bb_qoff.ensure(b * 8));
+    HIP_TRY(c, c->bb_flags.ensure(b * 2));
+    HIP_TRY(c, c->h_bb.ensure(64));
+    DevBatchBuild d;
+    memset(&d, 0, sizeof(d));
+    d.records = in->records;
+    d.records_bytes = in->records_bytes;
+    d.read_rec_off = in->read_rec_off;
+    d.n_reads = nr;
+    d.n_contigs = in->n_contigs;
+    d.contig_name_off = in->contig_name_off;
+    d.contig_names = in->contig_names;
+    d.table = c->bb_table.as<uint32_t>();
+    d.table_mask = slots - 1;
+    d.plan = c->bb_plan.as<uint32_t>();
+    d.size = c->bb_size.as<unsigned long long>();
+    d.start = c->bb_start.as<unsigned long long>();
+    d.err_kind = c->bb_kind.as<uint32_t>();
+    d.err = c->bb_err.as<int>();
+    d.read_is_reverse = c->bb_rev.as<uint8_t>();
+    d.read_seq_len = c->bb_len.as<uint32_t>();
+    d.read_seq_off = c->bb_soff.as<uint64_t>();
+    d.read_qual_off = c->bb_qoff.as<uint64_t>();
+    d.read_flags = c->bb_flags.as<uint16_t>();
+    unsigned long long *start = c->bb_start.as<unsigned long long>();
+    unsigned long long *h = c->h_bb.as<unsigned long long>();
+    memset(h, 0, 64);
+    int *herr = (int *)(h + 2);  // [BB_ERR_WORDS], then the failing read's kind
+    herr[0] = BB_NO_READ;
+    if (nr) {
+        HIP_TRY(c, hipMemsetAsync(c->bb_table.p, 0, (size_t)slots * 4, st));
+        HIP_TRY(c, hipMemcpyAsync(c->bb_err.p, herr, BB_ERR_WORDS * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipEventRecord(c->bev[0], st));
+        if (in->n_contigs) hipLaunchKernelGGL(k_bb_table, dim3((in->n_contigs + 255) / 256), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(k_bb_plan, dim3((nr + 3) / 4), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 2), dim3(64), 0, st, (const unsigned long long *)d.size, nr, nb, c->bb_partial.as<unsigned long long>());
+        hipLaunchKernelGGL(k_rec_scan_partials, dim3(2), dim3(64), 0, st, c->bb_partial.as<unsigned long long>(), nr, nb, start);
+        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 2), dim3(64), 0, st, (const unsigned long long *)d.size, nr, nb, (const unsigned long long *)c->bb_partial.as<unsigned long long>(), start);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->bev[1], st));
+        // the one round trip for the sizes: total segments, total ops, the bounds counters and the lowest failing read
+        HIP_TRY(c, hipMemcpyAsync(h, start + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h + 1, start + (size_t)nr + 1 + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(herr, c->bb_err.p, BB_ERR_WORDS * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (herr[1 + REC_ERR_OFFSET] || herr[1 + REC_ERR_BLOCK] || herr[1 + REC_ERR_LAYOUT]) {
+            c->err = "plo_batch_build_dev: " + std::to_string(herr[1 + REC_ERR_OFFSET]) + " read_rec_off beyond records_bytes, " + std::to_string(herr[1 + REC_ERR_BLOCK]) +
+                     " block_size running past the end of `records`, " + std::to_string(herr[1 + REC_ERR_LAYOUT]) +
+                     " l_qname / n_cigar / l_seq pointing outside their record; no batch was built";
+            return PLO_ERR_INVALID_ARG;
+        }
+        if (herr[0] != BB_NO_READ) {
+            uint32_t kind = 0;
+            HIP_TRY(c, hipMemcpyAsync(&herr[BB_ERR_WORDS], d.err_kind + herr[0], 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            kind = (uint32_t)herr[BB_ERR_WORDS];
+            static const char *const what[] = {"no failure", "the SA aux field is not a string", "an SA segment without exactly six fields", "a malformed SA segment",
+                                               "an SA segment without an aligned op", "an SA segment whose read length differs from the primary record's",
+                                               "an SA segment on a contig the header does not name", "a split segment that covers no read base"};
+            out->err_read = (uint32_t)herr[0];
+            out->err_kind = kind;
+            c->err = "plo_batch_build_dev: read " + std::to_string(herr[0]) + ": " + (kind < 8 ? what[kind] : "?") + " (kind " + std::to_string(kind) + ")";
+            return PLO_ERR_DATA;
+        }
+    }
+    const unsigned long long ns = h[0], n_ops = h[1];
+    if (n_ops > 0x7fffffffull || ns > 0xfffffffeull) {
+        c->err = "plo_batch_build_dev: window carries more than 2^31 - 1 CIGAR ops; read fewer records per window";
+        return PLO_ERR_RANGE;
+    }
+    const size_t sb = std::max<size_t>(ns, 1);
+    HIP_TRY(c, c->bb_tkey.ensure(sb * 8));
+    HIP_TRY(c, c->bb_tnops.ensure(sb * 4));
+    HIP_TRY(c, c->bb_tctext.ensure(sb * 4));
+    HIP_TRY(c, c->bb_tclen.ensure(sb * 4));
+    HIP_TRY(c, c->bb_tcontig.ensure(sb * 4));
+    HIP_TRY(c, c->bb_tdst.ensure(sb * 4));
+    HIP_TRY(c, c->bb_tpos.ensure(sb * 8));
+    HIP_TRY(c, c->bb_tfwd.ensure(sb));
+    HIP_TRY(c, c->bb_sread.ensure(sb * 4));
+    HIP_TRY(c, c->bb_scontig.ensure(sb * 4));
+    HIP_TRY(c, c->bb_spos.ensure(sb * 8));
+    HIP_TRY(c, c->bb_sfwd.ensure(sb));
+    HIP_TRY(c, c->bb_coff.ensure((sb + 1) * 4));
+    HIP_TRY(c, c->bb_cigar.ensure(std::max<size_t>(n_ops, 1) * 4));
+    d.t_key = c->bb_tkey.as<unsigned long long>();
+    d.t_nops = c->bb_tnops.as<uint32_t>();
+    d.t_ctext = c->bb_tctext.as<uint32_t>();
+    d.t_clen = c->bb_tclen.as<uint32_t>();
+    d.t_contig = c->bb_tcontig.as<uint32_t>();
+    d.t_dst = c->bb_tdst.as<uint32_t>();
+    d.t_pos = c->bb_tpos.as<long long>();
+    d.t_fwd = c->bb_tfwd.as<uint8_t>();
+    d.seg_read = c->bb_sread.as<uint32_t>();
+    d.seg_contig = c->bb_scontig.as<uint32_t>();
+    d.seg_pos = c->bb_spos.as<int64_t>();
+    d.seg_fwd = c->bb_sfwd.as<uint8_t>();
+    d.seg_cigar_off = c->bb_coff.as<uint32_t>();
+    d.cigar = c->bb_cigar.as<uint32_t>();
+    float a_ms = 0, b_ms = 0;
+    if (nr) {
+        HIP_TRY(c, hipEventRecord(c->bev[2], st));
+        hipLaunchKernelGGL(k_bb_emit, dim3(std::min<uint32_t>((nr + 3) / 4, (uint32_t)std::max(1, c->n_cus) * 8u)), dim3(256), 0, st, d);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->bev[3], st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        (void)hipEventElapsedTime(&a_ms, c->bev[0], c->bev[1]);
+        (void)hipEventElapsedTime(&b_ms, c->bev[2], c->bev[3]);
+    } else {
+        HIP_TRY(c, hipMemsetAsync(c->bb_coff.p, 0, 4, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    out->batch_ms = a_ms + b_ms;
+    plo_batch_in &bi = out->batch;
+    bi.n_reads = nr;
+    bi.read_is_reverse = d.read_is_reverse;
+    bi.read_seq_len = d.read_seq_len;
+    bi.read_seq_off = d.read_seq_off;
+    bi.seq = in->records;
+    bi.seq_bytes = in->records_bytes;
+    bi.seq_fmt = PLO_SEQ_BAM4;
+    bi.n_segs = (uint32_t)ns;
+    bi.seg_read = d.seg_read;
+    bi.seg_contig = d.seg_contig;
+    bi.seg_pos = d.seg_pos;
+    bi.seg_is_fwd_strand = d.seg_fwd;
+    bi.seg_cigar_off = d.seg_cigar_off;
+    bi.cigar = d.cigar;
+    out->fin.read_flags = d.read_flags;
+    out->fin.qual = in->records;
+    out->fin.read_qual_off = d.read_qual_off;
+    out->fin.qual_bytes = in->records_bytes;
     return PLO_OK;
 }
 

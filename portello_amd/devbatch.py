@@ -350,6 +350,50 @@ def upload_raw_window(desc: abi.PloBatchIn, fin: abi.PloFinishIn, raw: abi.PloWi
                              up(raw.read_rec_off, np.uint64, n, np.int64))
 
 
+@dataclass
+class UploadedRecords:
+    """the window's stretch of the BAM stream and read_rec_off in HBM and nothing else (device_batch): the batch is built there
+    (api.Engine.batch_build_dev) and handed on by DeviceBuiltWindow; keeps the tensors alive"""
+    raw: torch.Tensor
+    raw_bytes: int
+    rec_off: torch.Tensor
+    n_reads: int
+
+    def build_in(self, labels) -> abi.PloBatchBuildIn:
+        """labels: contig_labels(...) of the read->contig BAM's @SQ names"""
+        n, t_off, t_blob = labels
+        return abi.PloBatchBuildIn(_p(self.raw, C.c_uint8), self.raw_bytes, _p(self.rec_off, C.c_uint64), self.n_reads, n, _p(t_off, C.c_uint32), _p(t_blob, C.c_uint8))
+
+
+def upload_records(raw: abi.PloWindowRaw, dev) -> UploadedRecords:
+    """copies what bam.Window.raw() describes to the device on torch's current stream: the records once and their offsets"""
+    n, nb = int(raw.n_reads), int(raw.raw_bytes)
+    t_raw = torch.from_numpy(_host_view(raw.raw, np.uint8, nb)).to(dev, non_blocking=True) if nb else torch.zeros(16, dtype=torch.uint8, device=dev)
+    t_off = (torch.from_numpy(_host_view(raw.read_rec_off, np.uint64, n).view(np.int64)).to(dev, non_blocking=True) if n
+             else torch.zeros(1, dtype=torch.int64, device=dev)[:0])
+    return UploadedRecords(t_raw, nb, t_off, n)
+
+
+class DeviceBuiltWindow:
+    """what UploadedRawWindow hands on, from a batch built on the device: the plo_batch_in / plo_finish_in of a plo_batch_build_out (arrays
+    owned by the engine's context until its next batch_build_dev) and the plo_records_in over the same uploaded records"""
+
+    def __init__(self, up: UploadedRecords, bo: abi.PloBatchBuildOut):
+        self.up, self.bo = up, bo
+        self.batch_ms = float(bo.batch_ms)
+
+    def desc(self) -> abi.PloBatchIn:
+        return self.bo.batch
+
+    def finish_in(self) -> abi.PloFinishIn:
+        return self.bo.fin
+
+    def records_in(self, labels, is_target_region: bool = False) -> abi.PloRecordsIn:
+        n, t_off, t_blob = labels
+        return abi.PloRecordsIn(_p(self.up.raw, C.c_uint8), self.up.raw_bytes, _p(self.up.rec_off, C.c_uint64), n, _p(t_off, C.c_uint32), _p(t_blob, C.c_uint8),
+                                1 if is_target_region else 0)
+
+
 def contig_labels(names, dev):
     """the PS:Z labels (the @SQ names of the read->contig BAM) as device arrays, as sa_inputs carries the reference's: (n, offsets, blob)"""
     sa, keep = sa_inputs(names, dev)

@@ -66,6 +66,7 @@ class PipelineStats:
     bgzf_device_ms: float = 0.0  # device_bgzf: HIP-event time of plo_bgzf_compress_dev (deflate / stored framing, scan, pack)
     out_file_bytes: int = 0      # size of the closed output file(s) of the lifted records (header and EOF blocks included)
     records_device_ms: float = 0.0  # device_records: HIP-event time of plo_records_build_dev (plan, scan, emit); build_s then holds only the host time left
+    batch_device_ms: float = 0.0  # device_batch: HIP-event time of plo_batch_build_dev (label table, plan, scans, emit); batch_s then holds only win.raw()
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -79,8 +80,13 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    cmdline: str = "", sparse_margin: Optional[int] = 32, device_inflate: Optional[bool] = True,
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
-                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False) -> PipelineStats:  # noqa: E501
-    """device_bgzf (default off; needs device_records=True): the window's record bytes are framed as BGZF blocks on the device too
+                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False) -> PipelineStats:  # noqa: E501
+    """device_batch (default off; needs device_records=True): the window's liftover batch is built on the device too -- the batcher thread
+    only asks the window for its raw stretch (bam.Window.raw), the records and read_rec_off go up, and plo_batch_build_dev (split segments,
+    SA parse, sort, label look-up, CIGAR gather) runs on the worker's stream in front of plo_liftover_batch_dev: no segment, CIGAR or
+    per-read array crosses the bus and the host parses no record.  Input the host batcher refuses (PLO_ERR_DATA) aborts the run as it does
+    there.  Same arrays as the host batcher's (tests/test_batch_dev.py).
+    device_bgzf (default off; needs device_records=True): the window's record bytes are framed as BGZF blocks on the device too
     (plo_bgzf_compress_dev behind plo_records_build_dev) and only the finished blocks come down; the writer appends them as they are
     (plo_bam_write_blocks: no CRC pass, no deflate on the host).  `level` then selects between the device's two forms: level == 0 is
     stored framing, byte for byte the host writer's; level >= 1 is the device's ONE deflate level (LZ77 + dynamic Huffman codes, about
@@ -113,6 +119,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if device_batch and not device_records:
+        raise ValueError("device_batch builds the batch from the records device_records uploads as they stand: it needs device_records=True")
     if device_bgzf and not device_records:
         raise ValueError("device_bgzf compresses the records plo_records_build_dev leaves on the device: it needs device_records=True")
     device_finish = bool(device_finish or device_records)
@@ -205,6 +213,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 t = time.perf_counter()
                 if not win.n_records:
                     desc = None
+                elif device_batch:
+                    desc = win.raw()  # plo_window_raw alone: the batch is built on the device
                 elif device_records:
                     desc = win.batch_raw()  # (plo_batch_in, plo_finish_in, plo_window_raw): nothing gathered, views into the records
                 elif device_finish:
@@ -259,9 +269,16 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                     if device_records:
                         marks = [("start", t)]
                         with torch.cuda.stream(tstream):
-                            up = devbatch.upload_raw_window(desc[0], desc[1], desc[2], dev)
-                            marks.append(("upload (issue)", time.perf_counter()))
-                            ddesc = up.batch.desc()
+                            if device_batch:
+                                ur = devbatch.upload_records(desc, dev)
+                                marks.append(("upload (issue)", time.perf_counter()))
+                                up = devbatch.DeviceBuiltWindow(ur, eng.batch_build_dev(ur.build_in(labels)))
+                                marks.append(("batch", time.perf_counter()))
+                                ddesc = up.desc()
+                            else:
+                                up = devbatch.upload_raw_window(desc[0], desc[1], desc[2], dev)
+                                marks.append(("upload (issue)", time.perf_counter()))
+                                ddesc = up.batch.desc()
                             out = eng.liftover_batch_dev(ddesc)
                             marks.append(("liftover", time.perf_counter()))
                             eng.compact_output_dev(out)
@@ -286,6 +303,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 st.lift_detail_s[name] = st.lift_detail_s.get(name, 0.0) + (b - a)
                             st.finish_device_ms += float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms)
                             st.records_device_ms += rb.records_ms
+                            st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up
                     elif device_finish:

@@ -9,10 +9,15 @@ For a chr20 window of --reads reads held in memory, JSON with
     compressed bytes and their D2H time beside the D2H of the raw bytes, payload GB/s through the kernels beside the 16-thread host writer
     at the same level on the same bytes; every block is inflated with zlib and compared.  With --e2e-reads also run_bam_to_bam with the
     host writer against device_bgzf, at level 0 and at --level, three alternating runs each.
+  - plo_batch_build_dev on the uploaded records (--batch-out; this leg runs alone): batch_ms (HIP events) and the call's wall time beside
+    the wall time of the host's plo_bam_window_batch_raw with --threads threads on the same window, the bytes of segment / CIGAR / per-read
+    arrays whose upload it saves and the time of that upload; every array is compared with the host's.  With --e2e-reads also
+    run_bam_to_bam device_records against device_records + device_batch, three alternating runs each.
 Exits non-zero on any byte mismatch between the device's records and the host's.
 
     python tools/bench_records.py --reads 50000 --out profiles/r07_records_window.json
     python tools/bench_records.py --reads 50000 --level 1 --bgzf-out profiles/r08_bgzf_window.json --e2e-reads 180000
+    python tools/bench_records.py --reads 50000 --batch-out profiles/r09_batch_window.json --e2e-reads 180000
 """
 import argparse
 import ctypes as C
@@ -107,6 +112,101 @@ def end_to_end_bgzf(n_reads, level):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def end_to_end_batch(n_reads):
+    """run_bam_to_bam reads/s with device_records=True: the host batcher against device_batch, three alternating runs each"""
+    import shutil
+
+    from portello_amd import api, bamsynth, pipeline, synth
+
+    w = synth.generate(synth.config("chr20", n_reads=n_reads), device="cuda")
+    d = tempfile.mkdtemp(prefix="plo_batch_e2e_")
+    try:
+        inp = os.path.join(d, "reads.bam")
+        meta = bamsynth.write_read_bam(w, inp, level=1, n_threads=16)
+        ixd = w.index_data()
+        index = api.Index(w.index_data_device())
+        cn, rn, rl = meta["contig_names"], bamsynth.ref_names(w), [int(s.numel()) for s in w.chrom_seq]
+        kw = dict(window_reads=7500, n_workers=3, io_threads=16, out_shards=4, device_records=True)
+        pipeline.run_bam_to_bam(inp, os.path.join(d, "warm.bam"), index, ixd, cn, rn, rl, window_reads=2000, n_workers=1, device_records=True, device_batch=True)
+        runs = {"host_batch": [], "device_batch": []}
+        detail = {}
+        for k in range(3):
+            for mode in ("host_batch", "device_batch"):
+                st = pipeline.run_bam_to_bam(inp, os.path.join(d, f"{mode}_{k}.bam"), index, ixd, cn, rn, rl, device_batch=mode == "device_batch", **kw)
+                runs[mode].append(st.reads / st.seconds)
+                detail.setdefault(mode, []).append({"seconds": st.seconds, "batch_s": st.batch_s, "lift_s": st.lift_s, "write_s": st.write_s, "read_s": st.read_s,
+                                                    "batch_device_ms": st.batch_device_ms, "records_device_ms": st.records_device_ms, "records_out": st.records_out,
+                                                    "lift_detail_s": dict(st.lift_detail_s)})
+                for p_ in st.out_paths:
+                    os.unlink(p_)
+        index.close()
+        return {"reads": n_reads, "config": kw, "unit": "reads/s", **{m: {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": v} for m, v in runs.items()},
+                "run_detail": detail}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def batch_leg(a, win, index, cn, dev):
+    """ONE window: the host's plo_bam_window_batch_raw against plo_batch_build_dev on the uploaded records -> (JSON, arrays equal)"""
+    import numpy as np
+    import torch
+
+    from portello_amd import api, build, devbatch
+
+    def arr(ptr, dtype, count):
+        if not count:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype)
+
+    host_ms = []
+    for k in range(a.warmup + a.reps):
+        t = time.perf_counter()
+        b, f, r = win.batch_raw()  # (the window's own thread count: the reader's, --threads)
+        if k >= a.warmup:
+            host_ms.append((time.perf_counter() - t) * 1e3)
+    n, ns = int(b.n_reads), int(b.n_segs)
+    n_ops = int(arr(b.seg_cigar_off, np.uint32, ns + 1)[-1])
+    fields = (("read_is_reverse", np.uint8, n, b), ("read_seq_len", np.uint32, n, b), ("read_seq_off", np.uint64, n, b), ("read_flags", np.uint16, n, f),
+              ("read_qual_off", np.uint64, n, f), ("seg_read", np.uint32, ns, b), ("seg_contig", np.uint32, ns, b), ("seg_pos", np.int64, ns, b),
+              ("seg_is_fwd_strand", np.uint8, ns, b), ("seg_cigar_off", np.uint32, ns + 1, b), ("cigar", np.uint32, n_ops, b))
+    saved = sum(cnt * np.dtype(dt).itemsize for _, dt, cnt, _ in fields)
+    # the upload those arrays cost today: the whole raw window against the records + read_rec_off alone
+    h2d_full, h2d_raw = [], []
+    for k in range(a.warmup + a.reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        up_full = devbatch.upload_raw_window(b, f, r, dev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        ur = devbatch.upload_records(win.raw(), dev)
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            h2d_full.append((t1 - t) * 1e3)
+            h2d_raw.append((time.perf_counter() - t1) * 1e3)
+    del up_full
+    eng = api.Engine(index)
+    labels = devbatch.contig_labels(cn, dev)
+    torch.cuda.synchronize()
+    bin_ = ur.build_in(labels)
+    ms, wall = [], []
+    for k in range(a.warmup + a.reps):
+        t = time.perf_counter()
+        bo = eng.batch_build_dev(bin_)
+        if k >= a.warmup:
+            wall.append((time.perf_counter() - t) * 1e3)
+            ms.append(float(bo.batch_ms))
+    same = int(bo.batch.n_reads) == n and int(bo.batch.n_segs) == ns
+    for name, dt, cnt, src in fields:
+        same = same and np.array_equal(eng.download(getattr(bo.fin if src is f else bo.batch, name), dt, cnt), arr(getattr(src, name), dt, cnt))
+    eng.close()
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "segments": ns, "cigar_ops": n_ops, "raw_window_bytes": int(r.raw_bytes),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "arrays_equal_host": bool(same),
+           "host_window_batch_raw_ms": dict(stats(host_ms), threads=a.threads), "device_batch_ms": stats(ms), "device_batch_call_wall_ms": stats(wall),
+           "upload_bytes_saved": int(saved), "h2d_raw_window_with_batch_ms": stats(h2d_full), "h2d_records_only_ms": stats(h2d_raw)}
+    return res, bool(same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -119,6 +219,7 @@ def main():
     ap.add_argument("--e2e-reads", type=int, default=0, help="> 0: also run_bam_to_bam device_finish against device_records on that many reads, three runs each, alternating")
     ap.add_argument("--level", type=int, default=1, help="BGZF level of the compress step beside level 0 (the device has one deflate level: 1)")
     ap.add_argument("--bgzf-out", default="", help="run the compress step (plo_bgzf_compress_dev) and write its JSON there")
+    ap.add_argument("--batch-out", default="", help="run the batch-construction leg (plo_batch_build_dev) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -138,6 +239,20 @@ def main():
     rd = bam.BamReader(path, 8)
     win = rd.read_window(a.reads + 10)
     assert win.n_records == a.reads
+    if a.batch_out:
+        bres, ok = batch_leg(a, win, index, cn, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(a.batch_out)), exist_ok=True)
+        for part in ("window", "end_to_end"):  # the window's figures are on disk before the long runs start
+            if part == "end_to_end":
+                if a.e2e_reads <= 0:
+                    break
+                win.close()
+                rd.close()
+                bres["end_to_end"] = end_to_end_batch(a.e2e_reads)
+            with open(a.batch_out, "w") as fh:
+                fh.write(json.dumps(bres, indent=1) + "\n")
+        print(json.dumps(bres))
+        sys.exit(0 if ok else 1)
 
     def device_route(bytecopy):
         if bytecopy:
