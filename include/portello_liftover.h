@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 9 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw */
+#define PLO_API_VERSION 10 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -451,6 +451,85 @@ typedef struct plo_batch_build_out {
 } plo_batch_build_out;
 
 plo_status plo_batch_build_dev(plo_ctx *ctx, const plo_batch_build_in *in, plo_batch_build_out *out);
+
+/* ---- The input BAM stream (device-resident) ------------------------------------------------------------------------
+ * plo_bgzf_inflate_dev: the public, device-resident form of the reader's device inflate.  `bgzf` (HOST memory, pageable or page-locked)
+ * holds BGZF blocks from a block boundary on.  The headers are walked on the host with the reader's rules (gzip magic with FEXTRA, the
+ * `BC` subfield, BSIZE, the ISIZE trailer; ISIZE above 65536 is refused); every WHOLE block whose inflated bytes still fit in `dst` is
+ * taken, uploaded, inflated (k_bgzf_inflate) and checked against its CRC-32 (k_bgzf_crc) on the context's stream, and the inflated
+ * bytes are left packed at dst[0, n_bytes).  Nothing inflated is copied to the host.  A trailing partial block (fewer than 28 bytes
+ * left, or fewer than BSIZE) and the blocks from the first one that no longer fits are not consumed: bgzf_consumed says where to go on.
+ * A block with ISIZE 0 (the EOF block, wherever it stands) is consumed and adds nothing.  Bytes at a block boundary that are no BGZF
+ * header -> PLO_ERR_IO; a block that does not decode or fails its CRC -> PLO_ERR_IO, plo_last_error names the block's offset inside
+ * `bgzf` (the contents of dst are undefined then).  bgzf_bytes == 0: PLO_OK with nothing consumed.  The call returns when its kernels are
+ * through.  `dst` is a device buffer of the caller's; the compressed bytes are staged in a buffer the context owns. */
+typedef struct plo_bgzf_inflate_in {
+    const uint8_t *bgzf; /* host */
+    uint64_t bgzf_bytes;
+    uint8_t *dst;        /* device */
+    uint64_t dst_cap;
+} plo_bgzf_inflate_in;
+
+typedef struct plo_bgzf_inflate_out {
+    uint32_t n_blocks;      /* blocks consumed (those with ISIZE 0 included)            */
+    uint64_t bgzf_consumed; /* compressed bytes consumed: the next call's `bgzf` starts there */
+    uint64_t n_bytes;       /* inflated bytes at dst                                     */
+    float inflate_ms;       /* HIP-event time: upload, both kernels, the status download */
+} plo_bgzf_inflate_out;
+
+plo_status plo_bgzf_inflate_dev(plo_ctx *ctx, const plo_bgzf_inflate_in *in, plo_bgzf_inflate_out *out);
+
+/* plo_window_cut_dev: the record walk and the window cut of plo_bam_read_window (portello_bam.h) over stream[0, stream_bytes), a stretch of
+ * the inflated BAM stream in device memory that begins at a record boundary.  Record by record in stream order, exactly the host's loop:
+ *   - in front of every record, in this order: n_reads == max_records -> the window ends (PLO_CUT_MAX_RECORDS); n_unmapped >= max_unmapped
+ *     -> PLO_CUT_MAX_UNMAPPED; the record's offset >= max_bytes and at least one primary or unmapped record taken -> PLO_CUT_MAX_BYTES;
+ *   - then the record: no byte left -> PLO_CUT_EOF with final != 0, PLO_CUT_END_OF_BYTES otherwise; fewer than 4 bytes left or fewer than
+ *     4 + block_size -> with final == 0 the window ends IN FRONT of it with PLO_CUT_END_OF_BYTES (add bytes and cut again from the same
+ *     start), with final != 0 PLO_ERR_IO ("truncated BAM record"); block_size < 32 -> PLO_ERR_IO (this test comes before the one against
+ *     the bytes left, as on the host); fixed fields + name + CIGAR + bases + qualities beyond block_size -> PLO_ERR_IO; flag 0x4 with
+ *     tid >= 0 -> PLO_ERR_DATA; flag 0x4 -> an unmapped record; flag 0x800 -> skipped; anything else -> a primary read.
+ * On an error err_off is the offset of the FIRST offending record and nothing else of `out` may be used.  A bad record behind the point
+ * where the window ends does not fail this window: it fails the window it belongs to.
+ * max_unmapped / max_bytes == 0: the host's rule, 4 x max_records + 1024 and max(1 GB, min(8 GB, max_records << 16)).  max_records == 0 ->
+ * PLO_ERR_INVALID_ARG.  stream_bytes == 0: PLO_OK with zero records, PLO_CUT_EOF when final != 0, PLO_CUT_END_OF_BYTES otherwise.
+ * Every block_size is checked against stream_bytes before a byte behind it is read: nothing outside [stream, stream + stream_bytes) is read.
+ * The stretch is walked in segments of PLO_CUT_SEG_BYTES from guessed record boundaries (window_core.hpp); the guesses are hints, the
+ * result is the serial walk's whatever they are.  The stream is waited for once for the counts that size the outputs and once behind the
+ * emit kernels.  All pointers are device pointers; outputs are owned by the context and valid until its next plo_window_cut_dev. */
+#define PLO_CUT_SEG_BYTES 32768u
+typedef enum plo_cut_end {
+    PLO_CUT_MAX_RECORDS = 0,
+    PLO_CUT_MAX_UNMAPPED = 1,
+    PLO_CUT_MAX_BYTES = 2,
+    PLO_CUT_END_OF_BYTES = 3, /* final == 0: the bytes ended (in front of a record, or inside the one at window_bytes) */
+    PLO_CUT_EOF = 4           /* final != 0 and the walk ended exactly at stream_bytes                                  */
+} plo_cut_end;
+
+typedef struct plo_window_cut_in {
+    const uint8_t *stream;
+    uint64_t stream_bytes;
+    uint32_t max_records;
+    uint64_t max_unmapped; /* 0: 4 x max_records + 1024                         */
+    uint64_t max_bytes;    /* 0: max(1 GB, min(8 GB, max_records << 16))         */
+    int32_t final;         /* nothing follows these bytes                        */
+} plo_window_cut_in;
+
+typedef struct plo_window_cut_out {
+    uint32_t n_reads;
+    const uint64_t *read_rec_off; /* [n_reads] offsets of the primary records' block_size words: what plo_batch_build_in / plo_records_in take */
+    uint32_t n_unmapped;
+    const uint64_t *unmapped_off; /* [n_unmapped + 1] offsets inside `unmapped`                                                */
+    const uint8_t *unmapped;      /* the unmapped records side by side in stream order, each with its block_size word: the bytes
+                                     plo_bam_window_unmapped returns                                                            */
+    uint64_t unmapped_bytes;
+    uint64_t window_bytes;        /* the stretch the window consumes; the next window starts there                              */
+    int32_t ended_by;             /* plo_cut_end                                                                                */
+    uint64_t err_off;             /* PLO_ERR_IO / PLO_ERR_DATA: offset of the first offending record, UINT64_MAX otherwise       */
+    float cut_ms;                 /* HIP-event time of the call's kernels                                                       */
+    uint32_t n_rewalks;           /* segments walked again because their guessed start was not the true one (a diagnostic)      */
+} plo_window_cut_out;
+
+plo_status plo_window_cut_dev(plo_ctx *ctx, const plo_window_cut_in *in, plo_window_cut_out *out);
 
 /* (plo_finish_batch_dev returns PLO_ERR_DATA when an item of the batch ended LEN_MISMATCH or PANIC -- the reference aborts
    there, :207-229 -- and leaves is_target_region handling (:318-320: no unmapped copy) to the caller.)

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 9  # include/portello_liftover.h
+PLO_API_VERSION = 10  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -206,6 +206,35 @@ class PloBatchBuildIn(C.Structure):
 
 class PloBatchBuildOut(C.Structure):
     _fields_ = [("batch", PloBatchIn), ("fin", PloFinishIn), ("err_read", C.c_uint32), ("err_kind", C.c_uint32), ("batch_ms", C.c_float)]
+
+
+# plo_cut_end: why a window of plo_window_cut_dev ended
+CUT_MAX_RECORDS = 0
+CUT_MAX_UNMAPPED = 1
+CUT_MAX_BYTES = 2
+CUT_END_OF_BYTES = 3
+CUT_EOF = 4
+CUT_SEG_BYTES = 32768
+CUT_NO_ERR = 0xFFFFFFFFFFFFFFFF
+
+
+class PloBgzfInflateIn(C.Structure):
+    _fields_ = [("bgzf", _u8p), ("bgzf_bytes", C.c_uint64), ("dst", _u8p), ("dst_cap", C.c_uint64)]
+
+
+class PloBgzfInflateOut(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint32), ("bgzf_consumed", C.c_uint64), ("n_bytes", C.c_uint64), ("inflate_ms", C.c_float)]
+
+
+class PloWindowCutIn(C.Structure):
+    _fields_ = [("stream", _u8p), ("stream_bytes", C.c_uint64), ("max_records", C.c_uint32), ("max_unmapped", C.c_uint64), ("max_bytes", C.c_uint64),
+                ("final", C.c_int32)]
+
+
+class PloWindowCutOut(C.Structure):
+    _fields_ = [("n_reads", C.c_uint32), ("read_rec_off", _u64p), ("n_unmapped", C.c_uint32), ("unmapped_off", _u64p), ("unmapped", _u8p),
+                ("unmapped_bytes", C.c_uint64), ("window_bytes", C.c_uint64), ("ended_by", C.c_int32), ("err_off", C.c_uint64), ("cut_ms", C.c_float),
+                ("n_rewalks", C.c_uint32)]
 
 
 class PloWindowRaw(C.Structure):  # include/portello_bam.h

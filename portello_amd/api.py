@@ -78,6 +78,12 @@ def load_library(path: Optional[str] = None):
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
+    L.plo_bgzf_inflate_dev.restype = C.c_int
+    L.plo_bgzf_inflate_dev.argtypes = [vp, C.POINTER(abi.PloBgzfInflateIn), C.POINTER(abi.PloBgzfInflateOut)]
+    L.plo_window_cut_dev.restype = C.c_int
+    L.plo_window_cut_dev.argtypes = [vp, C.POINTER(abi.PloWindowCutIn), C.POINTER(abi.PloWindowCutOut)]
+    L.plo_internal_window_cut_seg.restype = C.c_int
+    L.plo_internal_window_cut_seg.argtypes = [vp, C.POINTER(abi.PloWindowCutIn), C.POINTER(abi.PloWindowCutOut), C.c_uint64]
     L.plo_batch_build_dev.restype = C.c_int
     L.plo_batch_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchBuildIn), C.POINTER(abi.PloBatchBuildOut)]
     L.plo_bgzf_compress_dev.restype = C.c_int
@@ -242,6 +248,32 @@ class Engine:
             msg = self.lib.plo_last_error(self.handle)
             e = PortelloError(st, f"plo_batch_build_dev: {msg.decode() if msg else ''}")
             e.err_read, e.err_kind = int(out.err_read), int(out.err_kind)
+            raise e
+        return out
+
+    def bgzf_inflate_dev(self, bgzf, bgzf_bytes: int, dst, dst_cap: int) -> abi.PloBgzfInflateOut:
+        """The whole BGZF blocks at the HOST address `bgzf` inflated and CRC-checked on the device, their bytes left packed at the DEVICE
+        address `dst` (plo_bgzf_inflate_dev); blocks that no longer fit into dst_cap and a trailing partial block are not consumed."""
+        out = abi.PloBgzfInflateOut()
+        bin_ = abi.PloBgzfInflateIn(C.cast(C.c_void_p(int(bgzf)), abi._u8p), int(bgzf_bytes), C.cast(C.c_void_p(int(dst)), abi._u8p), int(dst_cap))
+        self._check(self.lib.plo_bgzf_inflate_dev(self.handle, C.byref(bin_), C.byref(out)), "plo_bgzf_inflate_dev")
+        return out
+
+    def window_cut_dev(self, stream, stream_bytes: int, max_records: int, final: bool, max_unmapped: int = 0, max_bytes: int = 0,
+                       seg_bytes: int = 0) -> abi.PloWindowCutOut:
+        """The window plo_bam_read_window would cut from the inflated BAM stream at the DEVICE address `stream` (plo_window_cut_dev); device
+        pointers out, valid until the engine's next window_cut_dev.  A refused record raises with `err_off` on the exception.  seg_bytes:
+        tests only, segments of another size than abi.CUT_SEG_BYTES."""
+        out = abi.PloWindowCutOut()
+        cin = abi.PloWindowCutIn(C.cast(C.c_void_p(int(stream)), abi._u8p), int(stream_bytes), int(max_records), int(max_unmapped), int(max_bytes), 1 if final else 0)
+        if seg_bytes:
+            st = self.lib.plo_internal_window_cut_seg(self.handle, C.byref(cin), C.byref(out), int(seg_bytes))
+        else:
+            st = self.lib.plo_window_cut_dev(self.handle, C.byref(cin), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_window_cut_dev: {msg.decode() if msg else ''}")
+            e.err_off = int(out.err_off)
             raise e
         return out
 

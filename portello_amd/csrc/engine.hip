@@ -41,6 +41,8 @@
 #include "finish_core.hpp"
 #include "records_core.hpp"
 #include "batch_core.hpp"
+#include "window_core.hpp"
+#include "bgzf_walk.hpp"
 #include "index_pack.hpp"
 #include "inflate.hpp"
 #include "deflate.hpp"
@@ -1325,6 +1327,33 @@ __global__ __launch_bounds__(256) void k_bb_emit(DevBatchBuild d) {
     for (uint32_t r = w; r < d.n_reads; r += nw) batch_emit_read(d, r);
 }
 
+// ---- the window cut (window_core.hpp) -------------------------------------------------------------------------------------------
+// guess: a wave per segment behind the first (segment 0 starts at offset 0)
+__global__ __launch_bounds__(256) void k_cut_guess(DevCut d) {
+    const uint32_t s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (s == 0 && wv::lane() == 0) d.guess[0] = 0;
+    if (s >= 1 && s < d.n_seg) cut_guess_segment(d, s);  // (wave-uniform)
+}
+// walk / find / emit: a lane per segment -- 64 independent chains per wave keep 64 loads in flight where one chain has one
+__global__ __launch_bounds__(64) void k_cut_walk(DevCut d) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < d.n_seg) (void)cut_walk_segment(d, s, d.guess[s], true);
+}
+__global__ __launch_bounds__(64) void k_cut_resolve(DevCut d) { cut_resolve(d); }
+__global__ __launch_bounds__(64) void k_cut_find(DevCut d) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < d.n_seg) cut_find_segment(d, s);
+}
+__global__ void k_cut_result(DevCut d) { cut_result(d); }
+__global__ __launch_bounds__(64) void k_cut_emit(DevCut d) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < d.n_seg) cut_emit_segment(d, s);
+}
+// the unmapped records side by side: a workgroup per record at a time, 16-byte stores
+__global__ __launch_bounds__(256) void k_cut_copy(DevCut d) {
+    for (unsigned long long u = blockIdx.x; u < d.n_unmapped; u += gridDim.x) cut_copy_unmapped(d, u, (int)threadIdx.x, (int)blockDim.x);
+}
+
 // ---- BGZF inflate (inflate.hpp): every block of a chunk of the BAM stream at once, one wave per block ----------------------
 struct BgzfBlk {
     unsigned long long coff, uoff;  // offsets of the block's deflate data / inflated bytes inside the chunk buffers
@@ -1549,7 +1578,11 @@ struct plo_ctx {
     // plo_batch_build_dev: buffers of its own (the label table, plan and scans, the segments in text order, the batch's arrays)
     DevBuf bb_table, bb_plan, bb_size, bb_start, bb_partial, bb_kind, bb_err, bb_tkey, bb_tnops, bb_tctext, bb_tclen, bb_tcontig, bb_tdst, bb_tpos, bb_tfwd,
         bb_rev, bb_len, bb_soff, bb_qoff, bb_flags, bb_sread, bb_scontig, bb_spos, bb_sfwd, bb_coff, bb_cigar;
-    HostBuf h_rec, h_bgzf, h_bb;
+    // plo_window_cut_dev / plo_bgzf_inflate_dev: buffers of their own
+    DevBuf wc_guess, wc_land, wc_cnt, wc_start, wc_partial, wc_fire, wc_res, wc_recoff, wc_unmoff, wc_unmsrc, wc_unm, ci_comp, ci_blk, ci_st;
+    HostBuf h_rec, h_bgzf, h_bb, h_wc, h_ci;
+    hipEvent_t wev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t iev[2] = {nullptr, nullptr};
     hipEvent_t zev[2] = {nullptr, nullptr};
     hipEvent_t bev[4] = {nullptr, nullptr, nullptr, nullptr};
     DevWork last_wk{};
@@ -1911,6 +1944,8 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_table, &c->bb_plan, &c->bb_size, &c->bb_start, &c->bb_partial, &c->bb_kind, &c->bb_err, &c->bb_tkey, &c->bb_tnops, &c->bb_tctext, &c->bb_tclen,
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
+                      &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm,
+                      &c->ci_comp, &c->ci_blk, &c->ci_st,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1920,7 +1955,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1932,6 +1967,10 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->zev[i]) (void)hipEventDestroy(c->zev[i]);
     for (int i = 0; i < 4; ++i)
         if (c->bev[i]) (void)hipEventDestroy(c->bev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->wev[i]) (void)hipEventDestroy(c->wev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->iev[i]) (void)hipEventDestroy(c->iev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -3661,6 +3700,183 @@ int plo_internal_bgzf_inflate(const uint8_t *comp, size_t comp_bytes, const void
     g_inf_cur = nullptr;
     return rc;
 }
+
+// The inflated BAM stream kept on the device: the header walk on the host (bgzf_walk.hpp), then upload, k_bgzf_inflate and k_bgzf_crc on the
+// context's stream straight into the caller's buffer -- plo_internal_bgzf_begin without its copy down.
+plo_status plo_bgzf_inflate_dev(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_bgzf_inflate_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    c->err.clear();
+    if (!in->bgzf_bytes) return PLO_OK;
+    if (!in->bgzf || (in->dst_cap && !in->dst)) {
+        c->err = "plo_bgzf_inflate_in: bgzf and dst are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    std::vector<BgzfWalkBlk> blks;
+    uint64_t consumed = 0, n_bytes = 0;
+    const int rc = bgzf_walk(in->bgzf, (size_t)in->bgzf_bytes, in->dst_cap, blks, &consumed, &n_bytes);
+    if (rc != BGZF_WALK_OK) {
+        c->err = std::string("plo_bgzf_inflate_dev: ") + (rc == BGZF_WALK_NOT_A_HEADER ? "not a BGZF block" : rc == BGZF_WALK_CORRUPT ? "corrupt BGZF block (no BC subfield, or a BSIZE below the header's own size)" : "BGZF block larger than 64 KiB") +
+                 " at offset " + std::to_string(consumed);
+        return PLO_ERR_IO;
+    }
+    out->bgzf_consumed = consumed;
+    out->n_bytes = n_bytes;
+    out->n_blocks = (uint32_t)blks.size();
+    const uint32_t n = (uint32_t)blks.size();
+    if (!n || !n_bytes) return PLO_OK;
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->iev[i]) HIP_TRY(c, hipEventCreate(&c->iev[i]));
+    const size_t blk_bytes = (size_t)n * sizeof(BgzfBlk), crc_bytes = (size_t)n * 4;
+    HIP_TRY(c, c->ci_comp.ensure((size_t)consumed + 16));
+    HIP_TRY(c, c->ci_blk.ensure(blk_bytes + crc_bytes));
+    HIP_TRY(c, c->ci_st.ensure((size_t)n * 4));
+    HIP_TRY(c, c->h_ci.ensure(blk_bytes + crc_bytes + (size_t)n * 4));
+    BgzfBlk *hb = c->h_ci.as<BgzfBlk>();
+    uint32_t *hcrc = (uint32_t *)((uint8_t *)c->h_ci.p + blk_bytes);
+    int *hst = (int *)((uint8_t *)c->h_ci.p + blk_bytes + crc_bytes);
+    for (uint32_t i = 0; i < n; ++i) {
+        hb[i] = BgzfBlk{blks[i].coff, blks[i].uoff, (uint32_t)blks[i].clen, (uint32_t)blks[i].ulen};
+        hcrc[i] = blks[i].crc;
+    }
+    HIP_TRY(c, hipEventRecord(c->iev[0], st));
+    HIP_TRY(c, hipMemcpyAsync(c->ci_comp.p, in->bgzf, (size_t)consumed, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->ci_blk.p, c->h_ci.p, blk_bytes + crc_bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3(std::min<uint32_t>((n + INF_WAVES - 1) / INF_WAVES, bgzf_workgroups())), dim3(INF_WAVES * 64), 0, st,
+                       (const uint8_t *)c->ci_comp.p, (const BgzfBlk *)c->ci_blk.p, n, in->dst, c->ci_st.as<int>());
+    hipLaunchKernelGGL(k_bgzf_crc, dim3(std::min<uint32_t>((n + INF_WAVES - 1) / INF_WAVES, (uint32_t)bgzf_workgroups() * 4u)), dim3(INF_WAVES * 64), 0, st,
+                       (const uint8_t *)in->dst, (const BgzfBlk *)c->ci_blk.p, n, (const uint32_t *)((const uint8_t *)c->ci_blk.p + blk_bytes), c->ci_st.as<int>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(hst, c->ci_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipEventRecord(c->iev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->inflate_ms, c->iev[0], c->iev[1]);
+    for (uint32_t i = 0; i < n; ++i)
+        if (hst[i] != 0) {
+            c->err = "plo_bgzf_inflate_dev: the BGZF block at offset " + std::to_string(blks[i].off) + (hst[i] == -10 ? " fails its CRC-32" : " does not decode (status " + std::to_string(hst[i]) + ")");
+            out->n_blocks = 0;
+            out->bgzf_consumed = 0;
+            out->n_bytes = 0;
+            return PLO_ERR_IO;
+        }
+    return PLO_OK;
+}
+
+// The windows of plo_bam_read_window cut on the device (window_core.hpp): k_cut_guess, k_cut_walk, k_cut_resolve, the 64-bit scans of the
+// segments' counts, k_cut_find, one wait for the result block, then k_cut_emit and k_cut_copy.
+static plo_status window_cut(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out, unsigned long long seg_bytes) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_off = UINT64_MAX;
+    c->err.clear();
+    if (!in->max_records || (in->stream_bytes && !in->stream) || seg_bytes < 64) {
+        c->err = "plo_window_cut_in: max_records and the stream are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const unsigned long long n = in->stream_bytes;
+    if (n / seg_bytes + 1 > 0x7ffffffeull) {
+        c->err = "plo_window_cut_dev: more than 2^31 - 2 segments";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->wev[i]) HIP_TRY(c, hipEventCreate(&c->wev[i]));
+    const uint32_t ns = (uint32_t)(n / seg_bytes + 1);
+    const uint32_t nb = (ns + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK;
+    HIP_TRY(c, c->wc_guess.ensure((size_t)ns * 8));
+    HIP_TRY(c, c->wc_land.ensure((size_t)ns * 8));
+    HIP_TRY(c, c->wc_cnt.ensure(3 * (size_t)ns * 8));
+    HIP_TRY(c, c->wc_start.ensure(3 * ((size_t)ns + 1) * 8));
+    HIP_TRY(c, c->wc_partial.ensure(3 * (size_t)nb * 8));
+    HIP_TRY(c, c->wc_fire.ensure(5 * (size_t)ns * 8));
+    HIP_TRY(c, c->wc_res.ensure(CR_WORDS * 8));
+    HIP_TRY(c, c->h_wc.ensure(CR_WORDS * 8));
+    DevCut d;
+    memset(&d, 0, sizeof(d));
+    d.stream = in->stream;
+    d.n = n;
+    d.seg_bytes = seg_bytes;
+    d.n_seg = ns;
+    d.max_records = in->max_records;
+    d.max_unmapped = in->max_unmapped ? in->max_unmapped : 4ull * in->max_records + 1024;
+    d.max_bytes = in->max_bytes ? in->max_bytes : std::max<unsigned long long>(1ull << 30, std::min<unsigned long long>(8ull << 30, (unsigned long long)in->max_records << 16));
+    d.final = in->final ? 1 : 0;
+    d.guess = c->wc_guess.as<unsigned long long>();
+    d.land = c->wc_land.as<unsigned long long>();
+    d.cnt = c->wc_cnt.as<unsigned long long>();
+    d.start = c->wc_start.as<unsigned long long>();
+    d.fire = c->wc_fire.as<unsigned long long>();
+    d.res = c->wc_res.as<unsigned long long>();
+    unsigned long long *start = c->wc_start.as<unsigned long long>();
+    unsigned long long *h = c->h_wc.as<unsigned long long>();
+    HIP_TRY(c, hipEventRecord(c->wev[0], st));
+    hipLaunchKernelGGL(k_cut_guess, dim3((ns + 3) / 4), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(k_cut_walk, dim3((ns + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_cut_resolve, dim3(1), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 3), dim3(64), 0, st, (const unsigned long long *)d.cnt, ns, nb, c->wc_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(3), dim3(64), 0, st, c->wc_partial.as<unsigned long long>(), ns, nb, start);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 3), dim3(64), 0, st, (const unsigned long long *)d.cnt, ns, nb, (const unsigned long long *)c->wc_partial.as<unsigned long long>(), start);
+    hipLaunchKernelGGL(k_cut_find, dim3((ns + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_cut_result, dim3(1), dim3(1), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->wev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, d.res, CR_WORDS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));  // the one round trip for the counts that size the outputs
+    const unsigned long long at = h[CR_AT], why = h[CR_WHY];
+    out->n_rewalks = (uint32_t)std::min<unsigned long long>(h[CR_REWALKS], 0xffffffffull);
+    if (at > n || why == CUT_NONE) {
+        c->err = "plo_window_cut_dev: no end of the window found (internal)";
+        return PLO_ERR_INTERNAL;
+    }
+    if (why >= CUT_WHY_ERR_TRUNC) {
+        out->err_off = at;
+        const char *what = why == CUT_WHY_ERR_TRUNC ? "truncated BAM record" : why == CUT_WHY_ERR_SHORT ? "BAM record shorter than its fixed fields" : why == CUT_WHY_ERR_LAYOUT ? "BAM record fields exceed its block_size"
+                                                                                                                                                                                  : "unmapped record placed on a contig (flag 0x4 with a reference id): the reference aborts on it (read_alignment_scanner.rs:396)";
+        c->err = std::string("plo_window_cut_dev: ") + what + " at offset " + std::to_string(at);
+        return why == CUT_WHY_ERR_UNM_TID ? PLO_ERR_DATA : PLO_ERR_IO;
+    }
+    if (h[CR_READS] > 0xfffffffeull || h[CR_UNMAPPED] > 0xfffffffeull) {
+        c->err = "plo_window_cut_dev: more than 2^32 - 2 records in the window";
+        return PLO_ERR_RANGE;
+    }
+    const unsigned long long nr = h[CR_READS], nu = h[CR_UNMAPPED], ub = h[CR_UNM_BYTES];
+    HIP_TRY(c, c->wc_recoff.ensure(std::max<size_t>(nr, 1) * 8));
+    HIP_TRY(c, c->wc_unmoff.ensure(((size_t)nu + 1) * 8));
+    HIP_TRY(c, c->wc_unmsrc.ensure(std::max<size_t>(nu, 1) * 8));
+    HIP_TRY(c, c->wc_unm.ensure(std::max<size_t>(ub, 16)));
+    d.cut_at = at;
+    d.read_rec_off = c->wc_recoff.as<uint64_t>();
+    d.unm_off = c->wc_unmoff.as<uint64_t>();
+    d.unm_src = c->wc_unmsrc.as<uint64_t>();
+    d.unmapped = c->wc_unm.as<uint8_t>();
+    d.n_unmapped = nu;
+    d.unmapped_bytes = ub;
+    HIP_TRY(c, hipEventRecord(c->wev[2], st));
+    hipLaunchKernelGGL(k_cut_emit, dim3((ns + 63) / 64), dim3(64), 0, st, d);
+    if (nu) hipLaunchKernelGGL(k_cut_copy, dim3((uint32_t)std::min<unsigned long long>(nu, (unsigned long long)std::max(1, c->n_cus) * 8ull)), dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->wev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float a_ms = 0, b_ms = 0;
+    (void)hipEventElapsedTime(&a_ms, c->wev[0], c->wev[1]);
+    (void)hipEventElapsedTime(&b_ms, c->wev[2], c->wev[3]);
+    out->cut_ms = a_ms + b_ms;
+    out->n_reads = (uint32_t)nr;
+    out->read_rec_off = d.read_rec_off;
+    out->n_unmapped = (uint32_t)nu;
+    out->unmapped_off = d.unm_off;
+    out->unmapped = d.unmapped;
+    out->unmapped_bytes = ub;
+    out->window_bytes = at;
+    out->ended_by = (int32_t)why;
+    return PLO_OK;
+}
+plo_status plo_window_cut_dev(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out) { return window_cut(c, in, out, PLO_CUT_SEG_BYTES); }
+// (tests: the same call with segments of another size; not part of the public ABI)
+plo_status plo_internal_window_cut_seg(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out, uint64_t seg_bytes) { return window_cut(c, in, out, seg_bytes); }
 
 plo_status plo_host_alloc(size_t bytes, void **out) {
     if (!out) return PLO_ERR_INVALID_ARG;

@@ -67,6 +67,8 @@ class PipelineStats:
     out_file_bytes: int = 0      # size of the closed output file(s) of the lifted records (header and EOF blocks included)
     records_device_ms: float = 0.0  # device_records: HIP-event time of plo_records_build_dev (plan, scan, emit); build_s then holds only the host time left
     batch_device_ms: float = 0.0  # device_batch: HIP-event time of plo_batch_build_dev (label table, plan, scans, emit); batch_s then holds only win.raw()
+    inflate_device_ms: float = 0.0  # device_input: HIP-event time of plo_bgzf_inflate_dev (upload, inflate, CRC)
+    cut_device_ms: float = 0.0      # device_input: HIP-event time of plo_window_cut_dev (guess, walk, resolve, scans, find, emit)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -80,8 +82,15 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    cmdline: str = "", sparse_margin: Optional[int] = 32, device_inflate: Optional[bool] = True,
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
-                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False) -> PipelineStats:  # noqa: E501
-    """device_batch (default off; needs device_records=True): the window's liftover batch is built on the device too -- the batcher thread
+                   out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
+                   device_input: bool = False) -> PipelineStats:  # noqa: E501
+    """device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1 and part None): the input's inflated
+    stream is made in device memory and stays there (devreader.DeviceBamReader: plo_bgzf_inflate_dev into a device buffer,
+    plo_window_cut_dev for the record walk and the window cut) -- a window reaches plo_batch_build_dev as a device buffer with its
+    read_rec_off, no inflated byte of a primary read comes down or goes up again; only the unmapped records are downloaded for the
+    pass-through.  Same windows as the host reader's (tests/test_window_cut_dev.py).  Parts of a file, as plo_bam_open_range cuts them
+    (part / n_parts, n_readers > 1), stay on the host reader: finding a part's first record on the device is out of scope here.
+    device_batch (default off; needs device_records=True): the window's liftover batch is built on the device too -- the batcher thread
     only asks the window for its raw stretch (bam.Window.raw), the records and read_rec_off go up, and plo_batch_build_dev (split segments,
     SA parse, sort, label look-up, CIGAR gather) runs on the worker's stream in front of plo_liftover_batch_dev: no segment, CIGAR or
     per-read array crosses the bus and the host parses no record.  Input the host batcher refuses (PLO_ERR_DATA) aborts the run as it does
@@ -119,6 +128,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if device_input and not device_batch:
+        raise ValueError("device_input hands plo_batch_build_dev windows that exist in device memory only: it needs device_batch=True (and device_records=True)")
+    if device_input and (int(n_readers) != 1 or part is not None):
+        raise ValueError("device_input reads the whole file with one reader: parts of a file (part / n_parts, n_readers > 1) stay on the host reader")
     if device_batch and not device_records:
         raise ValueError("device_batch builds the batch from the records device_records uploads as they stand: it needs device_records=True")
     if device_bgzf and not device_records:
@@ -132,7 +145,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     ixd = index_data.to_desc()
     n_readers = max(1, int(n_readers))
     dev_arg = (index.device if device_inflate else (-1 if device_inflate is False else None))
-    if n_readers == 1:
+    if device_input:
+        from . import devreader
+
+        rds = [devreader.DeviceBamReader(in_path, index)]
+    elif n_readers == 1:
         rds = [bam.BamReader(in_path, read_threads, device_inflate=dev_arg, part=part, n_parts=n_parts)]
     else:
         p0, np0 = (part or 0), max(1, n_parts)
@@ -213,6 +230,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 t = time.perf_counter()
                 if not win.n_records:
                     desc = None
+                elif device_input:
+                    desc = win  # (the records and read_rec_off are on the device already)
                 elif device_batch:
                     desc = win.raw()  # plo_window_raw alone: the batch is built on the device
                 elif device_records:
@@ -270,7 +289,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                         marks = [("start", t)]
                         with torch.cuda.stream(tstream):
                             if device_batch:
-                                ur = devbatch.upload_records(desc, dev)
+                                ur = (devbatch.UploadedRecords(desc.records, desc.records_bytes, desc.read_rec_off, desc.n_reads) if device_input
+                                      else devbatch.upload_records(desc, dev))
                                 marks.append(("upload (issue)", time.perf_counter()))
                                 up = devbatch.DeviceBuiltWindow(ur, eng.batch_build_dev(ur.build_in(labels)))
                                 marks.append(("batch", time.perf_counter()))
@@ -362,6 +382,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     def close_reader():
         t = time.perf_counter()
         for r_ in rds:
+            st.inflate_device_ms += getattr(r_, "inflate_ms", 0.0)
+            st.cut_device_ms += getattr(r_, "cut_ms", 0.0)
             r_.close()
         st.stage_done_s["reader closed"] = time.perf_counter() - t0
         st.stage_done_s["reader close took"] = time.perf_counter() - t

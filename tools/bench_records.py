@@ -13,11 +13,16 @@ For a chr20 window of --reads reads held in memory, JSON with
     the wall time of the host's plo_bam_window_batch_raw with --threads threads on the same window, the bytes of segment / CIGAR / per-read
     arrays whose upload it saves and the time of that upload; every array is compared with the host's.  With --e2e-reads also
     run_bam_to_bam device_records against device_records + device_batch, three alternating runs each.
+  - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
+    the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
+    window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
+    run_bam_to_bam device_records + device_batch against the same plus device_input, three alternating runs each.
 Exits non-zero on any byte mismatch between the device's records and the host's.
 
     python tools/bench_records.py --reads 50000 --out profiles/r07_records_window.json
     python tools/bench_records.py --reads 50000 --level 1 --bgzf-out profiles/r08_bgzf_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --batch-out profiles/r09_batch_window.json --e2e-reads 180000
+    python tools/bench_records.py --reads 50000 --cut-out profiles/r10_cut_window.json --e2e-reads 180000
 """
 import argparse
 import ctypes as C
@@ -146,6 +151,97 @@ def end_to_end_batch(n_reads):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def end_to_end_cut(n_reads):
+    """run_bam_to_bam reads/s with device_records + device_batch: the host reader against device_input, three alternating runs each"""
+    import shutil
+
+    from portello_amd import api, bamsynth, pipeline, synth
+
+    w = synth.generate(synth.config("chr20", n_reads=n_reads), device="cuda")
+    d = tempfile.mkdtemp(prefix="plo_cut_e2e_")
+    try:
+        inp = os.path.join(d, "reads.bam")
+        meta = bamsynth.write_read_bam(w, inp, level=1, n_threads=16)
+        ixd = w.index_data()
+        index = api.Index(w.index_data_device())
+        cn, rn, rl = meta["contig_names"], bamsynth.ref_names(w), [int(s.numel()) for s in w.chrom_seq]
+        kw = dict(window_reads=7500, n_workers=3, io_threads=16, out_shards=4, device_records=True, device_batch=True)
+        pipeline.run_bam_to_bam(inp, os.path.join(d, "warm.bam"), index, ixd, cn, rn, rl, window_reads=2000, n_workers=1, device_records=True, device_batch=True, device_input=True)
+        runs = {"host_input": [], "device_input": []}
+        detail = {}
+        for k in range(3):
+            for mode in ("host_input", "device_input"):
+                st = pipeline.run_bam_to_bam(inp, os.path.join(d, f"{mode}_{k}.bam"), index, ixd, cn, rn, rl, device_input=mode == "device_input", **kw)
+                runs[mode].append(st.reads / st.seconds)
+                detail.setdefault(mode, []).append({"seconds": st.seconds, "read_s": st.read_s, "batch_s": st.batch_s, "lift_s": st.lift_s, "write_s": st.write_s,
+                                                    "inflate_device_ms": st.inflate_device_ms, "cut_device_ms": st.cut_device_ms, "records_out": st.records_out,
+                                                    "lift_detail_s": dict(st.lift_detail_s)})
+                for p_ in st.out_paths:
+                    os.unlink(p_)
+        index.close()
+        return {"reads": n_reads, "config": kw, "unit": "reads/s", **{m: {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": v} for m, v in runs.items()},
+                "run_detail": detail}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def cut_leg(a, path, index, dev):
+    """ONE window: bam.BamReader.read_window + upload_records against inflate + cut on the device -> (JSON, results equal)"""
+    import numpy as np
+    import torch
+
+    from portello_amd import api, bam, build, devbatch, devreader
+
+    def host_route():
+        rd = bam.BamReader(path, a.threads)
+        t = time.perf_counter()
+        win = rd.read_window(a.reads + 10)
+        t1 = time.perf_counter()
+        ur = devbatch.upload_records(win.raw(), dev)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        return rd, win, ur, (t1 - t) * 1e3, (t2 - t1) * 1e3
+
+    def device_route():
+        rdr = devreader.DeviceBamReader(path, index)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        dw = rdr.read_window(a.reads + 10)
+        return rdr, dw, (time.perf_counter() - t) * 1e3
+
+    # compared before anything is timed
+    rd, win, ur, _, _ = host_route()
+    rdr, dw, _ = device_route()
+    raw = win.raw()
+    same = (dw.n_reads == int(raw.n_reads) and dw.records_bytes == int(raw.raw_bytes) and dw.unmapped_bytes() == win.unmapped_bytes() and
+            bool(torch.equal(dw.read_rec_off, ur.rec_off)) and bool(torch.equal(dw.records[:dw.records_bytes], ur.raw[:ur.raw_bytes])))
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "raw_window_bytes": int(raw.raw_bytes), "seg_bytes": 32768,
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "window_equal_host": bool(same), "refills": rdr.n_refills, "recuts": rdr.n_recuts}
+    win.close()
+    rd.close()
+    rdr.close()
+    del ur, dw
+    h_read, h_up, d_wall, d_inf, d_cut = [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        rd, win, ur, r_ms, u_ms = host_route()
+        win.close()
+        rd.close()
+        del ur
+        rdr, dw, w_ms = device_route()
+        if k >= a.warmup:
+            h_read.append(r_ms)
+            h_up.append(u_ms)
+            d_wall.append(w_ms)
+            d_inf.append(rdr.inflate_ms)
+            d_cut.append(rdr.cut_ms)
+        rdr.close()
+        del dw
+    res.update({"host_read_window_ms": dict(stats(h_read), threads=a.threads), "host_upload_records_ms": stats(h_up), "device_read_window_wall_ms": stats(d_wall),
+                "device_inflate_ms": stats(d_inf), "device_cut_ms": stats(d_cut)})
+    return res, bool(same)
+
+
 def batch_leg(a, win, index, cn, dev):
     """ONE window: the host's plo_bam_window_batch_raw against plo_batch_build_dev on the uploaded records -> (JSON, arrays equal)"""
     import numpy as np
@@ -220,6 +316,7 @@ def main():
     ap.add_argument("--level", type=int, default=1, help="BGZF level of the compress step beside level 0 (the device has one deflate level: 1)")
     ap.add_argument("--bgzf-out", default="", help="run the compress step (plo_bgzf_compress_dev) and write its JSON there")
     ap.add_argument("--batch-out", default="", help="run the batch-construction leg (plo_batch_build_dev) alone and write its JSON there")
+    ap.add_argument("--cut-out", default="", help="run the input leg (plo_bgzf_inflate_dev + plo_window_cut_dev) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -239,6 +336,20 @@ def main():
     rd = bam.BamReader(path, 8)
     win = rd.read_window(a.reads + 10)
     assert win.n_records == a.reads
+    if a.cut_out:
+        win.close()
+        rd.close()
+        cres, ok = cut_leg(a, path, index, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(a.cut_out)), exist_ok=True)
+        for part in ("window", "end_to_end"):
+            if part == "end_to_end":
+                if a.e2e_reads <= 0:
+                    break
+                cres["end_to_end"] = end_to_end_cut(a.e2e_reads)
+            with open(a.cut_out, "w") as fh:
+                fh.write(json.dumps(cres, indent=1) + "\n")
+        print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
     if a.batch_out:
         bres, ok = batch_leg(a, win, index, cn, dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.batch_out)), exist_ok=True)
