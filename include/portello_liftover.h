@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 10 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev */
+#define PLO_API_VERSION 11 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -502,7 +502,8 @@ typedef enum plo_cut_end {
     PLO_CUT_MAX_UNMAPPED = 1,
     PLO_CUT_MAX_BYTES = 2,
     PLO_CUT_END_OF_BYTES = 3, /* final == 0: the bytes ended (in front of a record, or inside the one at window_bytes) */
-    PLO_CUT_EOF = 4           /* final != 0 and the walk ended exactly at stream_bytes                                  */
+    PLO_CUT_EOF = 4,          /* final != 0 and the walk ended exactly at stream_bytes                                  */
+    PLO_CUT_PART_END = 5      /* plo_window_cut_part_dev: the record at window_bytes starts at or behind own_bytes      */
 } plo_cut_end;
 
 typedef struct plo_window_cut_in {
@@ -530,6 +531,80 @@ typedef struct plo_window_cut_out {
 } plo_window_cut_out;
 
 plo_status plo_window_cut_dev(plo_ctx *ctx, const plo_window_cut_in *in, plo_window_cut_out *out);
+
+/* ---- One PART of a BAM file on the device (API version 11) ----------------------------------------------------------
+ * The rule is plo_bam_open_range's (portello_bam.h): the compressed file is cut at size x part / n_parts, a part owns the records whose
+ * first byte lies in a BGZF block that STARTS inside its stretch [lo, hi), and reads on past hi to finish the last of them.
+ *
+ * plo_bgzf_inflate_part_dev: plo_bgzf_inflate_dev for a reader that knows where `bgzf` lies in its file (bgzf_file_off: the file offset
+ * of bgzf[0]) and where its part ends (range_end: the part's hi, UINT64_MAX = no end).  Same blocks, same bytes, same errors; in addition
+ * own_bytes: the offset inside dst of the first consumed block whose file offset is >= range_end, n_bytes when there is none.  (A block
+ * with ISIZE 0 holds no byte: a byte belongs to the last block that starts at or before it, so an empty block at the border changes
+ * nothing.)  Host arithmetic in the header walk; the kernels are plo_bgzf_inflate_dev's. */
+typedef struct plo_bgzf_inflate_part_in {
+    const uint8_t *bgzf; /* host */
+    uint64_t bgzf_bytes;
+    uint8_t *dst;        /* device */
+    uint64_t dst_cap;
+    uint64_t bgzf_file_off;
+    uint64_t range_end;
+} plo_bgzf_inflate_part_in;
+
+typedef struct plo_bgzf_inflate_part_out {
+    uint32_t n_blocks;
+    uint64_t bgzf_consumed;
+    uint64_t n_bytes;
+    float inflate_ms;
+    uint64_t own_bytes; /* records that start at dst + own_bytes or behind it are the next part's */
+} plo_bgzf_inflate_part_out;
+
+plo_status plo_bgzf_inflate_part_dev(plo_ctx *ctx, const plo_bgzf_inflate_part_in *in, plo_bgzf_inflate_part_out *out);
+
+/* plo_window_cut_part_dev: plo_window_cut_dev with the host's range test in front of every record, where plo_bam_read_window has it:
+ * behind the three stop tests and the tests for "no byte left" and "fewer than 4 bytes left", in front of block_size < 32.  A record whose
+ * offset is >= own_bytes ends the window in front of it with PLO_CUT_PART_END (the host's eof of a part): whatever stands there or behind
+ * it, a refused record included, never fails this call.  own_bytes == UINT64_MAX: plo_window_cut_dev.  own_bytes counts from `stream`:
+ * a reader that cuts window after window moves it with the stream. */
+typedef struct plo_window_cut_part_in {
+    const uint8_t *stream;
+    uint64_t stream_bytes;
+    uint32_t max_records;
+    uint64_t max_unmapped;
+    uint64_t max_bytes;
+    int32_t final;
+    uint64_t own_bytes;
+} plo_window_cut_part_in;
+
+plo_status plo_window_cut_part_dev(plo_ctx *ctx, const plo_window_cut_part_in *in, plo_window_cut_out *out);
+
+/* plo_part_start_dev: where the first record of a part behind the first starts.  stream[0, stream_bytes) (device memory) begins at the
+ * first inflated byte of the part's first BGZF block, usually inside a record; n_ref is the header's reference count; final != 0 says that
+ * nothing follows these bytes.  The result is the host's (plo_bam_open_range) over the same bytes.  Every offset p with
+ * p + 36 <= stream_bytes is one of
+ *   accept: eight records follow each other from p, each of them plausible (block_size >= 32 and within the bytes, reference ids in
+ *           [-1, n_ref), a NUL-terminated name of at least one byte, fixed fields + name + CIGAR + bases + qualities within block_size,
+ *           CIGAR op codes 0 .. 8) -- or at least one does and the chain ends exactly at stream_bytes with final != 0;
+ *   cut:    at least one plausible record, then the bytes end inside a record or in front of one, with final == 0;
+ *   reject: anything else.
+ * The lowest p that is no reject decides: accept -> PLO_PART_FOUND with first_off = p; cut -> PLO_PART_NEED_MORE (call again from the
+ * same start with more bytes); none -> PLO_PART_NONE (with final != 0 and little data the stretch is the tail of one record: the part is
+ * empty; otherwise the host reports PLO_ERR_DATA).  Every block_size is compared with the bytes left before anything behind it is read. */
+typedef enum plo_part_kind { PLO_PART_FOUND = 0, PLO_PART_NEED_MORE = 1, PLO_PART_NONE = 2 } plo_part_kind;
+
+typedef struct plo_part_start_in {
+    const uint8_t *stream;
+    uint64_t stream_bytes;
+    uint32_t n_ref;
+    int32_t final;
+} plo_part_start_in;
+
+typedef struct plo_part_start_out {
+    int32_t kind;       /* plo_part_kind                                  */
+    uint64_t first_off; /* PLO_PART_FOUND: the first record's offset, UINT64_MAX otherwise */
+    float start_ms;     /* HIP-event time of the kernel                    */
+} plo_part_start_out;
+
+plo_status plo_part_start_dev(plo_ctx *ctx, const plo_part_start_in *in, plo_part_start_out *out);
 
 /* (plo_finish_batch_dev returns PLO_ERR_DATA when an item of the batch ended LEN_MISMATCH or PANIC -- the reference aborts
    there, :207-229 -- and leaves is_target_region handling (:318-320: no unmapped copy) to the caller.)

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 10  # include/portello_liftover.h
+PLO_API_VERSION = 11  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -214,6 +214,7 @@ CUT_MAX_UNMAPPED = 1
 CUT_MAX_BYTES = 2
 CUT_END_OF_BYTES = 3
 CUT_EOF = 4
+CUT_PART_END = 5  # plo_window_cut_part_dev: the next record starts at or behind own_bytes
 CUT_SEG_BYTES = 32768
 CUT_NO_ERR = 0xFFFFFFFFFFFFFFFF
 
@@ -235,6 +236,34 @@ class PloWindowCutOut(C.Structure):
     _fields_ = [("n_reads", C.c_uint32), ("read_rec_off", _u64p), ("n_unmapped", C.c_uint32), ("unmapped_off", _u64p), ("unmapped", _u8p),
                 ("unmapped_bytes", C.c_uint64), ("window_bytes", C.c_uint64), ("ended_by", C.c_int32), ("err_off", C.c_uint64), ("cut_ms", C.c_float),
                 ("n_rewalks", C.c_uint32)]
+
+
+# API 11: one part of a file on the device
+PART_FOUND = 0
+PART_NEED_MORE = 1
+PART_NONE = 2
+NO_RANGE_END = 0xFFFFFFFFFFFFFFFF
+
+
+class PloBgzfInflatePartIn(C.Structure):
+    _fields_ = [("bgzf", _u8p), ("bgzf_bytes", C.c_uint64), ("dst", _u8p), ("dst_cap", C.c_uint64), ("bgzf_file_off", C.c_uint64), ("range_end", C.c_uint64)]
+
+
+class PloBgzfInflatePartOut(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint32), ("bgzf_consumed", C.c_uint64), ("n_bytes", C.c_uint64), ("inflate_ms", C.c_float), ("own_bytes", C.c_uint64)]
+
+
+class PloWindowCutPartIn(C.Structure):
+    _fields_ = [("stream", _u8p), ("stream_bytes", C.c_uint64), ("max_records", C.c_uint32), ("max_unmapped", C.c_uint64), ("max_bytes", C.c_uint64),
+                ("final", C.c_int32), ("own_bytes", C.c_uint64)]
+
+
+class PloPartStartIn(C.Structure):
+    _fields_ = [("stream", _u8p), ("stream_bytes", C.c_uint64), ("n_ref", C.c_uint32), ("final", C.c_int32)]
+
+
+class PloPartStartOut(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("first_off", C.c_uint64), ("start_ms", C.c_float)]
 
 
 class PloWindowRaw(C.Structure):  # include/portello_bam.h

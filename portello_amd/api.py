@@ -82,6 +82,12 @@ def load_library(path: Optional[str] = None):
     L.plo_bgzf_inflate_dev.argtypes = [vp, C.POINTER(abi.PloBgzfInflateIn), C.POINTER(abi.PloBgzfInflateOut)]
     L.plo_window_cut_dev.restype = C.c_int
     L.plo_window_cut_dev.argtypes = [vp, C.POINTER(abi.PloWindowCutIn), C.POINTER(abi.PloWindowCutOut)]
+    L.plo_bgzf_inflate_part_dev.restype = C.c_int
+    L.plo_bgzf_inflate_part_dev.argtypes = [vp, C.POINTER(abi.PloBgzfInflatePartIn), C.POINTER(abi.PloBgzfInflatePartOut)]
+    L.plo_window_cut_part_dev.restype = C.c_int
+    L.plo_window_cut_part_dev.argtypes = [vp, C.POINTER(abi.PloWindowCutPartIn), C.POINTER(abi.PloWindowCutOut)]
+    L.plo_part_start_dev.restype = C.c_int
+    L.plo_part_start_dev.argtypes = [vp, C.POINTER(abi.PloPartStartIn), C.POINTER(abi.PloPartStartOut)]
     L.plo_internal_window_cut_seg.restype = C.c_int
     L.plo_internal_window_cut_seg.argtypes = [vp, C.POINTER(abi.PloWindowCutIn), C.POINTER(abi.PloWindowCutOut), C.c_uint64]
     L.plo_batch_build_dev.restype = C.c_int
@@ -275,6 +281,38 @@ class Engine:
             e = PortelloError(st, f"plo_window_cut_dev: {msg.decode() if msg else ''}")
             e.err_off = int(out.err_off)
             raise e
+        return out
+
+    def bgzf_inflate_part_dev(self, bgzf, bgzf_bytes: int, dst, dst_cap: int, bgzf_file_off: int, range_end: int = abi.NO_RANGE_END) -> abi.PloBgzfInflatePartOut:
+        """bgzf_inflate_dev for a part of a file (plo_bgzf_inflate_part_dev): `bgzf` lies at bgzf_file_off of the file and the part ends at
+        range_end; own_bytes of the result is where, inside dst, the first block of the next part's stretch starts (n_bytes: nowhere)."""
+        out = abi.PloBgzfInflatePartOut()
+        bin_ = abi.PloBgzfInflatePartIn(C.cast(C.c_void_p(int(bgzf)), abi._u8p), int(bgzf_bytes), C.cast(C.c_void_p(int(dst)), abi._u8p), int(dst_cap),
+                                        int(bgzf_file_off), int(range_end))
+        self._check(self.lib.plo_bgzf_inflate_part_dev(self.handle, C.byref(bin_), C.byref(out)), "plo_bgzf_inflate_part_dev")
+        return out
+
+    def window_cut_part_dev(self, stream, stream_bytes: int, max_records: int, final: bool, own_bytes: int, max_unmapped: int = 0,
+                            max_bytes: int = 0) -> abi.PloWindowCutOut:
+        """window_cut_dev with the host's range test (plo_window_cut_part_dev): a record at or behind own_bytes ends the window in front of it
+        with abi.CUT_PART_END, whatever stands there."""
+        out = abi.PloWindowCutOut()
+        cin = abi.PloWindowCutPartIn(C.cast(C.c_void_p(int(stream)), abi._u8p), int(stream_bytes), int(max_records), int(max_unmapped), int(max_bytes),
+                                     1 if final else 0, int(own_bytes))
+        st = self.lib.plo_window_cut_part_dev(self.handle, C.byref(cin), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_window_cut_part_dev: {msg.decode() if msg else ''}")
+            e.err_off = int(out.err_off)
+            raise e
+        return out
+
+    def part_start_dev(self, stream, stream_bytes: int, n_ref: int, final: bool) -> abi.PloPartStartOut:
+        """Where the first record of a part starts in the inflated bytes at the DEVICE address `stream`, which begin with the part's first
+        BGZF block (plo_part_start_dev): kind abi.PART_FOUND with first_off, PART_NEED_MORE (ask again with more bytes) or PART_NONE."""
+        out = abi.PloPartStartOut()
+        pin = abi.PloPartStartIn(C.cast(C.c_void_p(int(stream)), abi._u8p), int(stream_bytes), int(n_ref), 1 if final else 0)
+        self._check(self.lib.plo_part_start_dev(self.handle, C.byref(pin), C.byref(out)), "plo_part_start_dev")
         return out
 
     def bgzf_compress_dev(self, dev_bytes, n_bytes: int, level: int) -> abi.PloBgzfOut:

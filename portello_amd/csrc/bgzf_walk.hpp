@@ -19,11 +19,15 @@ enum { BGZF_WALK_OK = 0, BGZF_WALK_NOT_A_HEADER = 1, BGZF_WALK_CORRUPT = 2, BGZF
 
 // Every whole block of b[0, n) whose inflated bytes still fit into `cap`.  *consumed: where the first block that was not taken starts (a
 // partial one, or one that no longer fits).  A failure's *consumed is the offset of the offending block.
-inline int bgzf_walk(const uint8_t *b, size_t n, uint64_t cap, std::vector<BgzfWalkBlk> &out, uint64_t *consumed, uint64_t *n_bytes) {
+// A part of a file (plo_bgzf_inflate_part_dev): b[0] lies at `file_off` of its file and the part ends at `range_end`; *own_bytes is the
+// inflated offset of the first block taken whose file offset is >= range_end, *n_bytes when there is none (BgzfIn::block_file_off: a byte
+// belongs to the last block that starts at or before it, so a block with ISIZE 0 at the border changes nothing).
+inline int bgzf_walk(const uint8_t *b, size_t n, uint64_t cap, std::vector<BgzfWalkBlk> &out, uint64_t *consumed, uint64_t *n_bytes, uint64_t file_off = 0,
+                     uint64_t range_end = UINT64_MAX, uint64_t *own_bytes = nullptr) {
     auto rd16 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); };
     auto rd32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
     size_t c = 0;
-    uint64_t u = 0;
+    uint64_t u = 0, own = UINT64_MAX;
     out.clear();
     int rc = BGZF_WALK_OK;
     while (c < n) {
@@ -65,12 +69,14 @@ inline int bgzf_walk(const uint8_t *b, size_t n, uint64_t cap, std::vector<BgzfW
             break;
         }
         if (u + k.ulen > cap) break;  // no longer fits
+        if (own == UINT64_MAX && range_end != UINT64_MAX && (file_off > range_end || c >= range_end - file_off)) own = u;
         u += k.ulen;
         c += bsize;
         out.push_back(k);
     }
     *consumed = c;
     *n_bytes = u;
+    if (own_bytes) *own_bytes = own == UINT64_MAX ? u : own;
     return rc;
 }
 

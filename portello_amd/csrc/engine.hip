@@ -1350,6 +1350,15 @@ __global__ __launch_bounds__(64) void k_cut_emit(DevCut d) {
     if (s < d.n_seg) cut_emit_segment(d, s);
 }
 // the unmapped records side by side: a workgroup per record at a time, 16-byte stores
+// the first record of a part (window_core.hpp): a wave takes tiles of candidates by ticket, in ascending order, until one lies above a find
+__global__ __launch_bounds__(256) void k_part_start(DevPart d) {
+    for (;;) {
+        unsigned long long t = 0;
+        if (wv::lane() == 0) t = wv::atomic_add_global(d.res + PS_TICKET, 1ull);
+        t = wv::bcast_first(t);
+        if (t >= d.n_tiles || !part_start_tile(d, t)) return;  // (wave-uniform)
+    }
+}
 __global__ __launch_bounds__(256) void k_cut_copy(DevCut d) {
     for (unsigned long long u = blockIdx.x; u < d.n_unmapped; u += gridDim.x) cut_copy_unmapped(d, u, (int)threadIdx.x, (int)blockDim.x);
 }
@@ -1579,7 +1588,7 @@ struct plo_ctx {
     DevBuf bb_table, bb_plan, bb_size, bb_start, bb_partial, bb_kind, bb_err, bb_tkey, bb_tnops, bb_tctext, bb_tclen, bb_tcontig, bb_tdst, bb_tpos, bb_tfwd,
         bb_rev, bb_len, bb_soff, bb_qoff, bb_flags, bb_sread, bb_scontig, bb_spos, bb_sfwd, bb_coff, bb_cigar;
     // plo_window_cut_dev / plo_bgzf_inflate_dev: buffers of their own
-    DevBuf wc_guess, wc_land, wc_cnt, wc_start, wc_partial, wc_fire, wc_res, wc_recoff, wc_unmoff, wc_unmsrc, wc_unm, ci_comp, ci_blk, ci_st;
+    DevBuf wc_guess, wc_land, wc_cnt, wc_start, wc_partial, wc_fire, wc_res, wc_recoff, wc_unmoff, wc_unmsrc, wc_unm, ci_comp, ci_blk, ci_st, ps_res;
     HostBuf h_rec, h_bgzf, h_bb, h_wc, h_ci;
     hipEvent_t wev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t iev[2] = {nullptr, nullptr};
@@ -1944,7 +1953,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_table, &c->bb_plan, &c->bb_size, &c->bb_start, &c->bb_partial, &c->bb_kind, &c->bb_err, &c->bb_tkey, &c->bb_tnops, &c->bb_tctext, &c->bb_tclen,
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
-                      &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm,
+                      &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
                       &c->ci_comp, &c->ci_blk, &c->ci_st,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
@@ -3703,9 +3712,10 @@ int plo_internal_bgzf_inflate(const uint8_t *comp, size_t comp_bytes, const void
 
 // The inflated BAM stream kept on the device: the header walk on the host (bgzf_walk.hpp), then upload, k_bgzf_inflate and k_bgzf_crc on the
 // context's stream straight into the caller's buffer -- plo_internal_bgzf_begin without its copy down.
-plo_status plo_bgzf_inflate_dev(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_bgzf_inflate_out *out) {
-    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+// (a part of a file, plo_bgzf_inflate_part_dev: where bgzf[0] lies in the file and where the part ends -> *own_bytes, bgzf_walk.hpp)
+static plo_status bgzf_inflate(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_bgzf_inflate_out *out, uint64_t file_off, uint64_t range_end, uint64_t *own_bytes) {
     memset(out, 0, sizeof(*out));
+    *own_bytes = 0;
     c->err.clear();
     if (!in->bgzf_bytes) return PLO_OK;
     if (!in->bgzf || (in->dst_cap && !in->dst)) {
@@ -3714,7 +3724,7 @@ plo_status plo_bgzf_inflate_dev(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_b
     }
     std::vector<BgzfWalkBlk> blks;
     uint64_t consumed = 0, n_bytes = 0;
-    const int rc = bgzf_walk(in->bgzf, (size_t)in->bgzf_bytes, in->dst_cap, blks, &consumed, &n_bytes);
+    const int rc = bgzf_walk(in->bgzf, (size_t)in->bgzf_bytes, in->dst_cap, blks, &consumed, &n_bytes, file_off, range_end, own_bytes);
     if (rc != BGZF_WALK_OK) {
         c->err = std::string("plo_bgzf_inflate_dev: ") + (rc == BGZF_WALK_NOT_A_HEADER ? "not a BGZF block" : rc == BGZF_WALK_CORRUPT ? "corrupt BGZF block (no BC subfield, or a BSIZE below the header's own size)" : "BGZF block larger than 64 KiB") +
                  " at offset " + std::to_string(consumed);
@@ -3759,14 +3769,33 @@ plo_status plo_bgzf_inflate_dev(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_b
             out->n_blocks = 0;
             out->bgzf_consumed = 0;
             out->n_bytes = 0;
+            *own_bytes = 0;
             return PLO_ERR_IO;
         }
     return PLO_OK;
 }
+plo_status plo_bgzf_inflate_dev(plo_ctx *c, const plo_bgzf_inflate_in *in, plo_bgzf_inflate_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    uint64_t own = 0;
+    return bgzf_inflate(c, in, out, 0, UINT64_MAX, &own);
+}
+plo_status plo_bgzf_inflate_part_dev(plo_ctx *c, const plo_bgzf_inflate_part_in *in, plo_bgzf_inflate_part_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    const plo_bgzf_inflate_in pin = {in->bgzf, in->bgzf_bytes, in->dst, in->dst_cap};
+    plo_bgzf_inflate_out po;
+    uint64_t own = 0;
+    const plo_status st = bgzf_inflate(c, &pin, &po, in->bgzf_file_off, in->range_end, &own);
+    out->n_blocks = po.n_blocks;
+    out->bgzf_consumed = po.bgzf_consumed;
+    out->n_bytes = po.n_bytes;
+    out->inflate_ms = po.inflate_ms;
+    out->own_bytes = own;
+    return st;
+}
 
 // The windows of plo_bam_read_window cut on the device (window_core.hpp): k_cut_guess, k_cut_walk, k_cut_resolve, the 64-bit scans of the
 // segments' counts, k_cut_find, one wait for the result block, then k_cut_emit and k_cut_copy.
-static plo_status window_cut(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out, unsigned long long seg_bytes) {
+static plo_status window_cut(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out, unsigned long long seg_bytes, uint64_t own_bytes = UINT64_MAX) {
     if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     out->err_off = UINT64_MAX;
@@ -3804,6 +3833,8 @@ static plo_status window_cut(plo_ctx *c, const plo_window_cut_in *in, plo_window
     d.max_unmapped = in->max_unmapped ? in->max_unmapped : 4ull * in->max_records + 1024;
     d.max_bytes = in->max_bytes ? in->max_bytes : std::max<unsigned long long>(1ull << 30, std::min<unsigned long long>(8ull << 30, (unsigned long long)in->max_records << 16));
     d.final = in->final ? 1 : 0;
+    d.ranged = own_bytes != UINT64_MAX;
+    d.own_bytes = own_bytes;
     d.guess = c->wc_guess.as<unsigned long long>();
     d.land = c->wc_land.as<unsigned long long>();
     d.cnt = c->wc_cnt.as<unsigned long long>();
@@ -3875,8 +3906,67 @@ static plo_status window_cut(plo_ctx *c, const plo_window_cut_in *in, plo_window
     return PLO_OK;
 }
 plo_status plo_window_cut_dev(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out) { return window_cut(c, in, out, PLO_CUT_SEG_BYTES); }
+plo_status plo_window_cut_part_dev(plo_ctx *c, const plo_window_cut_part_in *in, plo_window_cut_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    const plo_window_cut_in win = {in->stream, in->stream_bytes, in->max_records, in->max_unmapped, in->max_bytes, in->final};
+    return window_cut(c, &win, out, PLO_CUT_SEG_BYTES, in->own_bytes);
+}
 // (tests: the same call with segments of another size; not part of the public ABI)
 plo_status plo_internal_window_cut_seg(plo_ctx *c, const plo_window_cut_in *in, plo_window_cut_out *out, uint64_t seg_bytes) { return window_cut(c, in, out, seg_bytes); }
+
+// The first record of a part (window_core.hpp): k_part_start over tiles of PART_TILE candidates, then one wait for the two minima.
+static constexpr unsigned long long PART_TILE = 256;
+plo_status plo_part_start_dev(plo_ctx *c, const plo_part_start_in *in, plo_part_start_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->kind = PLO_PART_NONE;
+    out->first_off = UINT64_MAX;
+    c->err.clear();
+    if (in->stream_bytes && !in->stream) {
+        c->err = "plo_part_start_in: the stream is required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (in->stream_bytes < 36) return PLO_OK;  // (no candidate)
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->wev[i]) HIP_TRY(c, hipEventCreate(&c->wev[i]));
+    HIP_TRY(c, c->ps_res.ensure(PS_WORDS * 8));
+    HIP_TRY(c, c->h_wc.ensure(CR_WORDS * 8));
+    DevPart d;
+    memset(&d, 0, sizeof(d));
+    d.stream = in->stream;
+    d.n = in->stream_bytes;
+    d.n_cand = d.n - 35;
+    d.tile = PART_TILE;
+    d.n_tiles = (d.n_cand + d.tile - 1) / d.tile;
+    d.n_ref = in->n_ref;
+    d.final = in->final ? 1 : 0;
+    d.res = c->ps_res.as<unsigned long long>();
+    unsigned long long *h = c->h_wc.as<unsigned long long>();
+    const uint32_t waves = (uint32_t)std::min<unsigned long long>(d.n_tiles, (unsigned long long)std::max(1, c->n_cus) * 8ull);
+    HIP_TRY(c, hipEventRecord(c->wev[0], st));
+    HIP_TRY(c, hipMemsetAsync(d.res, 0xff, 2 * 8, st));
+    HIP_TRY(c, hipMemsetAsync(d.res + PS_TICKET, 0, 8, st));
+    hipLaunchKernelGGL(k_part_start, dim3((waves + 3) / 4), dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->wev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, d.res, 2 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->start_ms, c->wev[0], c->wev[1]);
+    const unsigned long long acc = h[PS_ACCEPT], cut = h[PS_CUT];
+    if ((acc != CUT_NONE && acc >= d.n_cand) || (cut != CUT_NONE && cut >= d.n_cand)) {
+        c->err = "plo_part_start_dev: a candidate outside the stretch (internal)";
+        return PLO_ERR_INTERNAL;
+    }
+    if (acc < cut) {
+        out->kind = PLO_PART_FOUND;
+        out->first_off = acc;
+    } else if (cut != CUT_NONE) {
+        out->kind = PLO_PART_NEED_MORE;
+    }
+    return PLO_OK;
+}
 
 plo_status plo_host_alloc(size_t bytes, void **out) {
     if (!out) return PLO_ERR_INVALID_ARG;

@@ -13,6 +13,8 @@
 //   scan    (waves):               the 64-bit exclusive scans of records_core.hpp over the three counts of every segment
 //   find    (a lane per segment):  the host loop's stop tests in its order in front of every record, then its refusals; the lowest offset
 //                                  at which one of them fires is where the window ends
+//                                  (a part of a file: the host's range test stands among them, a record at or behind own_bytes ends the
+//                                  window with PLO_CUT_PART_END; the walks may run past own_bytes, their counts there are never used)
 //   emit    (a lane per segment):  read_rec_off and the unmapped records' places, then their bytes with copy_span (a workgroup per record)
 // The chain ends in exactly one TERMINAL position: the end of the bytes, a record the bytes cut short, or a record the host refuses.
 // Position stream_bytes itself belongs to the last segment (n / seg_bytes + 1 segments), so the end of the bytes is classified like a record.
@@ -49,6 +51,8 @@ struct DevCut {
     uint32_t n_seg;                // n / seg_bytes + 1
     unsigned long long max_records, max_unmapped, max_bytes;
     int final;
+    int ranged;                    // a part of a file (plo_window_cut_part_dev): records at or behind own_bytes are the next part's
+    unsigned long long own_bytes;  // offset of the first block that starts in the next part's stretch (BgzfIn::range_end as an inflated offset)
     // per segment
     unsigned long long *guess;        // entry: the guess, from resolve on the true entry of a live segment, CUT_NONE of a dead one
     unsigned long long *land;         // where the walk from `guess` left the segment, CUT_NONE: it met the terminal position
@@ -218,6 +222,8 @@ PLO_DEV void cut_find_segment(const DevCut &d, uint32_t s) {
         else {
             const int k = cut_classify(d, at, bs);
             if (k == CUT_T_END) why = d.final ? (unsigned long long)PLO_CUT_EOF : (unsigned long long)PLO_CUT_END_OF_BYTES;
+            else if (k == CUT_T_TRUNC && d.n - at < 4) why = d.final ? (unsigned long long)CUT_WHY_ERR_TRUNC : (unsigned long long)PLO_CUT_END_OF_BYTES;
+            else if (d.ranged && at >= d.own_bytes) why = PLO_CUT_PART_END;  // (the host's range test, bam_host.cpp:268: in front of block_size < 32)
             else if (k == CUT_T_TRUNC) why = d.final ? (unsigned long long)CUT_WHY_ERR_TRUNC : (unsigned long long)PLO_CUT_END_OF_BYTES;
             else if (k == CUT_T_SHORT) why = CUT_WHY_ERR_SHORT;
             else if (k == CUT_T_LAYOUT) why = CUT_WHY_ERR_LAYOUT;
@@ -278,6 +284,80 @@ PLO_DEV void cut_emit_segment(const DevCut &d, uint32_t s) {
 // unmapped record u by nt cooperating threads
 PLO_DEV void cut_copy_unmapped(const DevCut &d, unsigned long long u, int tid, int nt) {
     copy_span<true>(d.unmapped + d.unm_off[u], d.stream + d.unm_src[u], d.unm_off[u + 1] - d.unm_off[u], tid, nt);
+}
+
+// ---- the first record of a part (plo_part_start_dev) ---------------------------------------------------------------------------------
+// The loop of plo_bam_open_range (bam_host.cpp:183-202) over stream[0, n), the inflated bytes from the first byte of the part's first block:
+// every candidate offset p with p + 36 <= n is an ACCEPT (a chain of eight plausible records, or of at least one that ends exactly at n with
+// `final`), a CUT (a chain of at least one that the end of the bytes cuts short, without `final`: the host buffers more) or a reject; the
+// lowest p that is no reject decides.  A lane per candidate, 64 candidates per wave step, tiles of `tile` candidates dealt in ascending order;
+// the lowest accept and the lowest cut are kept in two 64-bit minima, and a wave leaves when its step lies above one of them: whatever it
+// would find there is not the lowest, so the result does not depend on which waves left.
+enum { PS_ACCEPT = 0, PS_CUT = 1, PS_TICKET = 2, PS_WORDS = 4 };
+
+struct DevPart {
+    const uint8_t *stream;
+    unsigned long long n;       // stream_bytes
+    unsigned long long n_cand;  // candidates: n - 35, or 0
+    unsigned long long tile;    // candidates per tile, a multiple of 64
+    unsigned long long n_tiles;
+    uint32_t n_ref;
+    int final;
+    unsigned long long *res;  // [PS_WORDS]: both minima CUT_NONE and the ticket 0 at launch
+};
+
+// plausible_record (bam_host.cpp:113-130) in full, the reference ids against the header's list included: 0 = no record here, 1 = a record
+// (len), 2 = the bytes end inside it (what the host's `ran_out` says of a record plausible_record refused).  q <= n
+PLO_DEV int part_plausible(const DevPart &d, unsigned long long q, unsigned long long &len) {
+    if (d.n - q < 36) return 2;
+    const uint8_t *p = d.stream + q;
+    const uint32_t bs = rec_rd32(p);
+    if (bs < 32) return 0;
+    if (bs > d.n - q - 4) return 2;  // (before anything behind the fixed fields is read)
+    p += 4;
+    const int32_t tid = (int32_t)rec_rd32(p), mtid = (int32_t)rec_rd32(p + 20), n_ref = (int32_t)d.n_ref;
+    if (tid < -1 || tid >= n_ref || mtid < -1 || mtid >= n_ref) return 0;
+    const uint32_t lq = p[8], ncg = rec_rd16(p + 12), lseq = rec_rd32(p + 16);
+    if (lq < 1 || 32ull + lq + 4ull * ncg + (uint32_t)(lseq + 1u) / 2u + lseq > bs) return 0;
+    if (p[32 + lq - 1] != 0) return 0;
+    for (uint32_t i = 0; i < ncg; ++i)
+        if ((p[32 + lq + 4 * i] & 15u) > 8u) return 0;
+    len = 4ull + bs;
+    return 1;
+}
+// candidate p (p + 36 <= n): 0 = reject, 1 = accept, 2 = cut
+PLO_DEV int part_candidate(const DevPart &d, unsigned long long p) {
+    unsigned long long q = p, len = 0;
+    int ok = 0, r = 1;
+    while (ok < 8 && !(q == d.n && d.final) && (r = part_plausible(d, q, len)) == 1) {
+        q += len;
+        ++ok;
+    }
+    if (ok == 8 || (ok > 0 && q == d.n && d.final)) return 1;
+    return r == 2 && !d.final && ok > 0 ? 2 : 0;
+}
+PLO_DEV unsigned long long part_peek_u64(const unsigned long long *p) {
+#ifdef PLO_EMULATOR
+    return *p;
+#else
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+// the wave's tile t (< n_tiles).  false: this tile reaches above a candidate that is no reject, and so does every later one
+PLO_DEV bool part_start_tile(const DevPart &d, unsigned long long t) {
+    const unsigned long long lo = t * d.tile, hi = lo + d.tile < d.n_cand ? lo + d.tile : d.n_cand, lane = (unsigned long long)wv::lane();
+    for (unsigned long long c0 = lo; c0 < hi; c0 += 64) {  // (uniform)
+        const unsigned long long a = part_peek_u64(d.res + PS_ACCEPT), b = part_peek_u64(d.res + PS_CUT);
+        if (c0 > wv::bcast_first(a < b ? a : b)) return false;
+        const unsigned long long c = c0 + lane;
+        const int k = c < hi ? part_candidate(d, c) : 0;
+        const unsigned long long m = wv::ballot(k != 0);
+        if (m) {
+            if (lane == (unsigned long long)__builtin_ctzll(m)) cut_min_u64(d.res + (k == 1 ? PS_ACCEPT : PS_CUT), c);
+            return false;
+        }
+    }
+    return true;
 }
 
 }  // namespace plo

@@ -69,6 +69,7 @@ class PipelineStats:
     batch_device_ms: float = 0.0  # device_batch: HIP-event time of plo_batch_build_dev (label table, plan, scans, emit); batch_s then holds only win.raw()
     inflate_device_ms: float = 0.0  # device_input: HIP-event time of plo_bgzf_inflate_dev (upload, inflate, CRC)
     cut_device_ms: float = 0.0      # device_input: HIP-event time of plo_window_cut_dev (guess, walk, resolve, scans, find, emit)
+    part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -84,12 +85,14 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
                    device_input: bool = False) -> PipelineStats:  # noqa: E501
-    """device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1 and part None): the input's inflated
+    """device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1): the input's inflated
     stream is made in device memory and stays there (devreader.DeviceBamReader: plo_bgzf_inflate_dev into a device buffer,
     plo_window_cut_dev for the record walk and the window cut) -- a window reaches plo_batch_build_dev as a device buffer with its
     read_rec_off, no inflated byte of a primary read comes down or goes up again; only the unmapped records are downloaded for the
-    pass-through.  Same windows as the host reader's (tests/test_window_cut_dev.py).  Parts of a file, as plo_bam_open_range cuts them
-    (part / n_parts, n_readers > 1), stay on the host reader: finding a part's first record on the device is out of scope here.
+    pass-through.  Same windows as the host reader's (tests/test_window_cut_dev.py).  With part / n_parts the device reader takes this
+    process's part of the file as plo_bam_open_range cuts it (plo_part_start_dev finds the part's first record, plo_bgzf_inflate_part_dev
+    and plo_window_cut_part_dev end it where the next part's blocks begin: tests/test_part_dev.py).  One device reader per process is the
+    design -- a rank is a process with a GPU and a part -- so n_readers > 1 stays on the host reader.
     device_batch (default off; needs device_records=True): the window's liftover batch is built on the device too -- the batcher thread
     only asks the window for its raw stretch (bam.Window.raw), the records and read_rec_off go up, and plo_batch_build_dev (split segments,
     SA parse, sort, label look-up, CIGAR gather) runs on the worker's stream in front of plo_liftover_batch_dev: no segment, CIGAR or
@@ -130,8 +133,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
     if device_input and not device_batch:
         raise ValueError("device_input hands plo_batch_build_dev windows that exist in device memory only: it needs device_batch=True (and device_records=True)")
-    if device_input and (int(n_readers) != 1 or part is not None):
-        raise ValueError("device_input reads the whole file with one reader: parts of a file (part / n_parts, n_readers > 1) stay on the host reader")
+    if device_input and int(n_readers) != 1:
+        raise ValueError("device_input reads the file (or this process's part of it) with one reader: n_readers > 1 stays on the host reader")
     if device_batch and not device_records:
         raise ValueError("device_batch builds the batch from the records device_records uploads as they stand: it needs device_records=True")
     if device_bgzf and not device_records:
@@ -148,7 +151,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     if device_input:
         from . import devreader
 
-        rds = [devreader.DeviceBamReader(in_path, index)]
+        rds = [devreader.DeviceBamReader(in_path, index, part=part, n_parts=n_parts)]
     elif n_readers == 1:
         rds = [bam.BamReader(in_path, read_threads, device_inflate=dev_arg, part=part, n_parts=n_parts)]
     else:
@@ -384,6 +387,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         for r_ in rds:
             st.inflate_device_ms += getattr(r_, "inflate_ms", 0.0)
             st.cut_device_ms += getattr(r_, "cut_ms", 0.0)
+            st.part_start_device_ms += getattr(r_, "part_start_ms", 0.0)
             r_.close()
         st.stage_done_s["reader closed"] = time.perf_counter() - t0
         st.stage_done_s["reader close took"] = time.perf_counter() - t

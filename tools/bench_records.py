@@ -13,6 +13,8 @@ For a chr20 window of --reads reads held in memory, JSON with
     the wall time of the host's plo_bam_window_batch_raw with --threads threads on the same window, the bytes of segment / CIGAR / per-read
     arrays whose upload it saves and the time of that upload; every array is compared with the host's.  With --e2e-reads also
     run_bam_to_bam device_records against device_records + device_batch, three alternating runs each.
+  - plo_part_start_dev and the first cut of part 1 of 2 of the window's file against plo_bam_open_range and its first window on the host
+    (--part-out; this leg runs alone)
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -23,6 +25,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --level 1 --bgzf-out profiles/r08_bgzf_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --batch-out profiles/r09_batch_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --cut-out profiles/r10_cut_window.json --e2e-reads 180000
+    python tools/bench_records.py --reads 50000 --part-out profiles/r11_part_start.json
 """
 import argparse
 import ctypes as C
@@ -242,6 +245,62 @@ def cut_leg(a, path, index, dev):
     return res, bool(same)
 
 
+def part_leg(a, path, index):
+    """part 1 of 2 of the window's file: plo_bam_open_range + the first read_window on the host against DeviceBamReader(part=1, n_parts=2)
+    + its first read_window (plo_part_start_dev inside the open) -> (JSON, first windows equal)"""
+    import torch
+
+    from portello_amd import bam, build, devreader
+
+    mr = max(1, a.reads // 4)
+
+    def host_route():
+        t = time.perf_counter()
+        rd = bam.BamReader(path, a.threads, part=1, n_parts=2)
+        t1 = time.perf_counter()
+        win = rd.read_window(mr)
+        return rd, win, (t1 - t) * 1e3, (time.perf_counter() - t1) * 1e3
+
+    def device_route():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        rdr = devreader.DeviceBamReader(path, index, part=1, n_parts=2)
+        t1 = time.perf_counter()
+        dw = rdr.read_window(mr)
+        return rdr, dw, (t1 - t) * 1e3, (time.perf_counter() - t1) * 1e3
+
+    rd, win, _, _ = host_route()
+    rdr, dw, _, _ = device_route()
+    raw = win.raw()
+    same = (dw.n_reads == int(raw.n_reads) and dw.records_bytes == int(raw.raw_bytes) and dw.unmapped_bytes() == win.unmapped_bytes() and
+            dw.records[:dw.records_bytes].cpu().numpy().tobytes() == bytes(bytearray(raw.raw[:int(raw.raw_bytes)])))
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "part": 1, "n_parts": 2, "first_window_reads": int(raw.n_reads), "first_window_bytes": int(raw.raw_bytes),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "first_window_equal_host": bool(same), "part_start_calls": rdr.n_start_calls}
+    win.close()
+    rd.close()
+    rdr.close()
+    del dw
+    h_open, h_win, d_open, d_win, d_start, d_cut = [], [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        rd, win, o_ms, w_ms = host_route()
+        win.close()
+        rd.close()
+        rdr, dw, do_ms, dw_ms = device_route()
+        if k >= a.warmup:
+            h_open.append(o_ms)
+            h_win.append(w_ms)
+            d_open.append(do_ms)
+            d_win.append(dw_ms)
+            d_start.append(rdr.part_start_ms)
+            d_cut.append(rdr.cut_ms)
+        rdr.close()
+        del dw
+    res.update({"host_open_range_ms": dict(stats(h_open), threads=a.threads), "host_first_window_ms": stats(h_win), "device_open_wall_ms": stats(d_open),
+                "device_first_window_wall_ms": stats(d_win), "device_part_start_ms": stats(d_start), "device_first_cut_ms": stats(d_cut)})
+    return res, bool(same)
+
+
 def batch_leg(a, win, index, cn, dev):
     """ONE window: the host's plo_bam_window_batch_raw against plo_batch_build_dev on the uploaded records -> (JSON, arrays equal)"""
     import numpy as np
@@ -317,6 +376,7 @@ def main():
     ap.add_argument("--bgzf-out", default="", help="run the compress step (plo_bgzf_compress_dev) and write its JSON there")
     ap.add_argument("--batch-out", default="", help="run the batch-construction leg (plo_batch_build_dev) alone and write its JSON there")
     ap.add_argument("--cut-out", default="", help="run the input leg (plo_bgzf_inflate_dev + plo_window_cut_dev) alone and write its JSON there")
+    ap.add_argument("--part-out", default="", help="run the part leg (plo_part_start_dev and the first cut of part 1 of 2 against plo_bam_open_range) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -336,6 +396,15 @@ def main():
     rd = bam.BamReader(path, 8)
     win = rd.read_window(a.reads + 10)
     assert win.n_records == a.reads
+    if a.part_out:
+        win.close()
+        rd.close()
+        pres, ok = part_leg(a, path, index)
+        os.makedirs(os.path.dirname(os.path.abspath(a.part_out)), exist_ok=True)
+        with open(a.part_out, "w") as fh:
+            fh.write(json.dumps(pres, indent=1) + "\n")
+        print(json.dumps(pres))
+        sys.exit(0 if ok else 1)
     if a.cut_out:
         win.close()
         rd.close()
