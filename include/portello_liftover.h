@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 11 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev */
+#define PLO_API_VERSION 12 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -378,6 +378,35 @@ typedef struct plo_records_out {
 } plo_records_out;
 
 plo_status plo_records_build_dev(plo_ctx *ctx, const plo_batch_in *in, const plo_records_in *rin, plo_records_out *out);
+
+/* ---- NM:i of the lifted records (device-resident, opt-in) ---------------------------------------------------------
+ * clone_record cuts NM (src/read_alignment_scanner.rs:105-118): the edit distance against the contig is wrong on the reference, and
+ * nothing puts the right one back -- the reference's answer is a samtools calmd pass over the sorted output.  plo_nm_dev counts it for
+ * every item with status PLO_ITEM_LIFTED from what the context holds already: the item's output CIGAR (as plo_records_build_dev writes
+ * it), the record's bases in the orientation the record carries them (plo_finish_out::rev_seq when item_seq_off != PLO_NO_FLIP, the
+ * batch's `seq` otherwise; BAM 4-bit, high nibble first) and the index's chrom_seq from item_ref_pos on.  The rule is calmd's
+ * (bam_md.c): M / = / X compare base by base -- with c1 the read's code and c2 the reference byte's code in "=ACMGRSVTWYHKDBN" (any other
+ * byte: 15) a pair matches iff c1 == 0, or c1 == c2 and c1 != 15 (N against N is a mismatch, R against R a match, a read '=' matches
+ * anything); I and D add their lengths; N, S, H, P add nothing.
+ * Call it after plo_liftover_batch_dev (+ plo_compact_output_dev) and plo_finish_batch_dev on the same context and batch.  Called out of
+ * order, after a batch with PLO_SEQ_BAM4_SPARSE or PLO_SEQ_ASCII bases, or on an index without chrom_seq -> PLO_ERR_INVALID_ARG.  A CIGAR
+ * that consumes more reference than the chromosome has behind item_ref_pos, or more bases than read_seq_len, is refused by a check on the
+ * device before any such base is read -> PLO_ERR_RANGE, err_item is the LOWEST such item, no result is handed out.
+ * While the context holds a result, plo_records_build_dev writes NM:i (always type i: 'N','M','i' + u32 LE, 7 bytes, the form calmd
+ * appends) into every lifted record, directly behind ZM:C and in front of SA:Z / CG:B,I; the unmapped copy gets none.  Without a result
+ * its bytes are the host builder's, as before.  The result is dropped by the context's next plo_liftover_batch* (and plo_finish_batch_dev)
+ * call, so a caller who does not ask for NM never sees it.  NM exists on this route only: plo_records_build and
+ * plo_records_build_finished (portello_bam.h) write no NM.  One launch, one wait.  Outputs are owned by the context, valid until its
+ * next plo_liftover_batch* call. */
+typedef struct plo_nm_out {
+    uint32_t n_items;
+    const uint32_t *item_nm;     /* [n_items] device; 0 for items that are not LIFTED */
+    uint64_t n_cmp_bases;        /* bases compared (M / = / X), whole batch */
+    uint32_t err_item;           /* PLO_ERR_RANGE: lowest offending item, UINT32_MAX otherwise */
+    float nm_ms;                 /* HIP-event time of the call's kernels */
+} plo_nm_out;
+
+plo_status plo_nm_dev(plo_ctx *ctx, const plo_batch_in *in, plo_nm_out *out);
 
 /* ---- BGZF blocks (device-resident) ------------------------------------------------------------------------------
  * Cuts the n_bytes at `bytes` -- any device buffer, typically plo_records_out::bytes -- into payloads of 0xff00 bytes (htslib's

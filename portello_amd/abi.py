@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 11  # include/portello_liftover.h
+PLO_API_VERSION = 12  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -181,6 +181,10 @@ class PloRecordsIn(C.Structure):
 class PloRecordsOut(C.Structure):
     _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("n_lifted", C.c_uint32),
                 ("n_unmapped_copies", C.c_uint32), ("records_ms", C.c_float)]
+
+
+class PloNmOut(C.Structure):
+    _fields_ = [("n_items", C.c_uint32), ("item_nm", _u32p), ("n_cmp_bases", C.c_uint64), ("err_item", C.c_uint32), ("nm_ms", C.c_float)]
 
 
 class PloBgzfOut(C.Structure):

@@ -76,6 +76,8 @@ def load_library(path: Optional[str] = None):
     L.plo_sa_segments_dev.argtypes = [vp, C.POINTER(abi.PloSaIn), C.POINTER(abi.PloSaOut)]
     L.plo_finish_batch_dev.restype = C.c_int
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
+    L.plo_nm_dev.restype = C.c_int
+    L.plo_nm_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloNmOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_bgzf_inflate_dev.restype = C.c_int
@@ -235,6 +237,20 @@ class Engine:
         """SA-tag segments of the last liftover + finish result (plo_sa_segments_dev); device pointers."""
         out = abi.PloSaOut()
         self._check(self.lib.plo_sa_segments_dev(self.handle, C.byref(sa_in), C.byref(out)), "plo_sa_segments_dev")
+        return out
+
+    def nm_dev(self, desc: abi.PloBatchIn) -> abi.PloNmOut:
+        """NM:i of every lifted item of the batch this context has just lifted, compacted and finished (plo_nm_dev): calmd's edit distance of
+        the output record against the index's chromosomes; device pointers out.  While the result stands (until the next lift call),
+        records_build_dev writes NM:i into every lifted record.  A CIGAR that leaves its chromosome or its read raises PortelloError with
+        status PLO_ERR_RANGE and the lowest such item in `err_item`."""
+        out = abi.PloNmOut()
+        st = self.lib.plo_nm_dev(self.handle, C.byref(desc), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_nm_dev: {msg.decode() if msg else ''}")
+            e.err_item = int(out.err_item)
+            raise e
         return out
 
     def records_build_dev(self, desc: abi.PloBatchIn, rin: abi.PloRecordsIn) -> abi.PloRecordsOut:

@@ -41,6 +41,7 @@
 #include "finish_core.hpp"
 #include "records_core.hpp"
 #include "batch_core.hpp"
+#include "nm_core.hpp"
 #include "window_core.hpp"
 #include "bgzf_walk.hpp"
 #include "index_pack.hpp"
@@ -1310,6 +1311,10 @@ __global__ __launch_bounds__(256) void k_rec_emit(DevBatch bt, DevWork wk, DevRe
     for (uint32_t r = blockIdx.x; r < bt.n_reads; r += gridDim.x) records_emit_read<VEC>(bt, wk, d, r, (int)threadIdx.x, (int)blockDim.x);
 }
 
+// ---- NM:i of the lifted records (nm_core.hpp) ------------------------------------------------------------------------------
+// persistent waves, items by ticket.  HBM-bound by design: per lifted item l_seq / 2 bytes of bases, ~l_seq bytes of reference, 4 x ops
+__global__ __launch_bounds__(256) void k_nm(DevBatch bt, DevWork wk, DevNm d) { nm_items(bt, wk, d); }
+
 // ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
 // the label table: a thread per contig name
 __global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
@@ -1597,6 +1602,10 @@ struct plo_ctx {
     DevWork last_wk{};
     DevBatch last_bt{};
     bool have_last = false, have_finish = false, have_sa = false;
+    bool have_nm = false;  // plo_nm_dev's result of the current batch: plo_records_build_dev writes NM:i from it; dropped by the next lift / finish
+    DevBuf nm_out, nm_blk;
+    HostBuf h_nm;
+    hipEvent_t nev[2] = {nullptr, nullptr};
     bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1954,7 +1963,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
-                      &c->ci_comp, &c->ci_blk, &c->ci_st,
+                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1964,7 +1973,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1980,6 +1989,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->wev[i]) (void)hipEventDestroy(c->wev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->iev[i]) (void)hipEventDestroy(c->iev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->nev[i]) (void)hipEventDestroy(c->nev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -2143,6 +2154,7 @@ plo_status plo_liftover_batch_dev(plo_ctx *c, const plo_batch_in *in, uint32_t s
     if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     c->err.clear();
+    c->have_nm = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     if (in->n_segs && (!in->seg_read || !in->seg_contig || !in->seg_pos || !in->seg_is_fwd_strand || !in->seg_cigar_off)) {
         c->err = "plo_batch_in: NULL segment array";
@@ -3012,6 +3024,7 @@ plo_status plo_finish_batch_dev(plo_ctx *c, const plo_batch_in *in, const plo_fi
     }
     c->have_finish = false;
     c->have_sa = false;
+    c->have_nm = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     hipStream_t st = c->stream;
     for (int i = 0; i < 3; ++i)
@@ -3238,6 +3251,7 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     d.rev_qual = c->f_rqual.as<uint8_t>();
     d.sa_off = c->sa_off.as<uint32_t>();
     d.sa_text = c->sa_text.as<uint8_t>();
+    d.item_nm = c->have_nm ? c->nm_out.as<uint32_t>() : nullptr;
     d.cs_is_fwd = c->ix->d.cs_is_fwd;
     d.contig_seg_off = c->ix->d.contig_seg_off;
     d.plan = c->r_plan.as<uint32_t>();
@@ -3299,6 +3313,82 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     out->record_off = d.record_off;
     out->n_unmapped_copies = (uint32_t)h[2];
     out->n_lifted = (uint32_t)(n_rec - h[2]);
+    return PLO_OK;
+}
+
+// NM:i of every lifted item (nm_core.hpp): one launch of persistent waves and one wait, for the refusal, the count and the event time.
+plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_item = UINT32_MAX;
+    c->err.clear();
+    c->have_nm = false;
+    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
+        c->err = "plo_nm_dev: the batch came with sparse or ASCII bases; NM is counted over complete BAM 4-bit bases (PLO_SEQ_BAM4)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
+        c->err = "plo_nm_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_finish) {
+        c->err = "plo_nm_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevIndex &ix = c->ix->d;
+    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
+        c->err = "plo_nm_dev: the index has no chrom_seq";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevWork &wk = c->last_wk;
+    const DevBatch &bt = c->last_bt;
+    const uint32_t n = wk.n_items;
+    if (n > (uint32_t)NM_NO_ITEM) {
+        c->err = "plo_nm_dev: more than 2^31 - 1 items in one batch";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->nev[i]) HIP_TRY(c, hipEventCreate(&c->nev[i]));
+    HIP_TRY(c, c->nm_out.ensure((size_t)std::max(1u, n) * 4));
+    HIP_TRY(c, c->nm_blk.ensure(16));  // n_cmp, err_item, ticket
+    HIP_TRY(c, c->h_nm.ensure(16));
+    DevNm d;
+    memset(&d, 0, sizeof(d));
+    d.item_seq_off = c->f_isoff.as<uint64_t>();
+    d.rev_seq = c->f_rseq.as<uint8_t>();
+    d.chrom_seq = ix.chrom_seq;
+    d.chrom_len = ix.chrom_len;
+    d.n_chroms = ix.n_chroms;
+    d.item_nm = c->nm_out.as<uint32_t>();
+    d.n_cmp = c->nm_blk.as<unsigned long long>();
+    d.err_item = c->nm_blk.as<int>() + 2;
+    d.ticket = c->nm_blk.as<unsigned>() + 3;
+    uint32_t *h = c->h_nm.as<uint32_t>();
+    h[0] = h[1] = h[3] = 0;
+    h[2] = (uint32_t)NM_NO_ITEM;
+    HIP_TRY(c, hipMemcpyAsync(c->nm_blk.p, h, 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->nev[0], st));
+    if (n) {
+        // as many waves as stay resident (82 VGPRs: five per SIMD, five workgroups of four per CU), never more than items
+        const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
+        hipLaunchKernelGGL(k_nm, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->nev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->nm_blk.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->nm_ms, c->nev[0], c->nev[1]);
+    if (h[2] != (uint32_t)NM_NO_ITEM) {
+        out->err_item = h[2];
+        c->err = "plo_nm_dev: the CIGAR of item " + std::to_string(h[2]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no NM is handed out";
+        return PLO_ERR_RANGE;
+    }
+    out->n_items = n;
+    out->item_nm = d.item_nm;
+    out->n_cmp_bases = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+    c->have_nm = true;
     return PLO_OK;
 }
 

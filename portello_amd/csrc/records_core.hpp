@@ -7,6 +7,7 @@
 //                             (bam_internal.hpp, bam_host.cpp) -> at most five cuts sorted by offset, the kept length, the read's bytes
 //   scan  (waves):            exclusive 64-bit scan of the reads' bytes and record counts
 //   emit  (a workgroup per read): every byte of the read's records, the bulk as aligned 16-byte stores
+// With DevRecords::item_nm (nm_core.hpp) every lifted record gets NM:i behind ZM:C; that is the one difference to the host builder.
 // The same functions run under the CPU emulator (tests/emu/emu_records.cpp).
 #pragma once
 #include <plo_wave.hpp>
@@ -45,6 +46,7 @@ struct DevRecords {
     const uint8_t *rev_seq, *rev_qual;
     const uint32_t *sa_off;
     const uint8_t *sa_text;
+    const uint32_t *item_nm;  // the context's plo_nm_dev result: NM:i behind ZM:C of every lifted record; NULL: no NM, the host builder's bytes
     // the index: strand of the contig segments (PS suffix)
     const uint8_t *cs_is_fwd;
     const uint32_t *contig_seg_off;
@@ -112,7 +114,7 @@ PLO_DEV unsigned long long rec_lifted_size(const DevBatch &bt, const DevWork &wk
     const uint32_t contig = bt.seg_contig[wk.item_seg[i]];
     unsigned long long sz = base + (nc <= 0xffffu ? 4ull * nc : 8ull + 8ull + 4ull * nc);  // bam_write1: placeholder + CG:B,I
     sz += 3ull + (d.contig_name_off[contig + 1] - d.contig_name_off[contig]) + 6u + dec_digits(wk.item_cseg[i]) + 1u + 1u;  // PS:Z{contig}_split{n}{+|-}\0
-    return sz + 4;  // ZM:C
+    return sz + 4 + (d.item_nm ? 7u : 0u);  // ZM:C, NM:i
 }
 
 // plan + size of read r by one wave (every lane computes the same values; lane 0 stores them)
@@ -451,8 +453,14 @@ PLO_DEV void records_emit_read(const DevBatch &bt, const DevWork &wk, const DevR
             t[3] = 'M';
             t[4] = 'C';
             t[5] = p[9];
+            if (d.item_nm) {  // NM:i, always type i: the form samtools calmd appends
+                t[6] = 'N';
+                t[7] = 'M';
+                t[8] = 'i';
+                rec_wr32(t + 9, d.item_nm[i]);
+            }
         }
-        q += 3ull + cnl + 6 + dg + 2 + 4;
+        q += 3ull + cnl + 6 + dg + 2 + 4 + (d.item_nm ? 7u : 0u);
         if (nl > 1) {  // SA:Z: the segments of the read's other records, in record order (:352-364)
             if (tid == 0) {
                 q[0] = 'S';

@@ -70,6 +70,7 @@ class PipelineStats:
     inflate_device_ms: float = 0.0  # device_input: HIP-event time of plo_bgzf_inflate_dev (upload, inflate, CRC)
     cut_device_ms: float = 0.0      # device_input: HIP-event time of plo_window_cut_dev (guess, walk, resolve, scans, find, emit)
     part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
+    nm_device_ms: float = 0.0  # emit_nm: HIP-event time of plo_nm_dev (NM:i of the lifted records)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -84,8 +85,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
-                   device_input: bool = False) -> PipelineStats:  # noqa: E501
-    """device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1): the input's inflated
+                   device_input: bool = False, emit_nm: bool = False) -> PipelineStats:  # noqa: E501
+    """emit_nm (default off; needs device_records=True): every lifted record leaves with NM:i, calmd's edit distance against the
+    reference chromosomes of the index (plo_nm_dev between the finishing and plo_records_build_dev, which then writes the field behind ZM:C);
+    the unmapped copies get none.  Works with device_batch, device_input, device_bgzf and part / n_parts.  Off, every byte is what it was.
+    device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1): the input's inflated
     stream is made in device memory and stays there (devreader.DeviceBamReader: plo_bgzf_inflate_dev into a device buffer,
     plo_window_cut_dev for the record walk and the window cut) -- a window reaches plo_batch_build_dev as a device buffer with its
     read_rec_off, no inflated byte of a primary read comes down or goes up again; only the unmapped records are downloaded for the
@@ -131,6 +135,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if emit_nm and not device_records:
+        raise ValueError("emit_nm counts NM on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
     if device_input and not device_batch:
         raise ValueError("device_input hands plo_batch_build_dev windows that exist in device memory only: it needs device_batch=True (and device_records=True)")
     if device_input and int(n_readers) != 1:
@@ -310,6 +316,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             marks.append(("finish", time.perf_counter()))
                             so = eng.sa_segments_dev(sa_in)
                             marks.append(("sa text", time.perf_counter()))
+                            nm_ms = 0.0
+                            if emit_nm:
+                                nm_ms = float(eng.nm_dev(ddesc).nm_ms)
+                                marks.append(("nm", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
                             if device_bgzf:
@@ -326,6 +336,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 st.lift_detail_s[name] = st.lift_detail_s.get(name, 0.0) + (b - a)
                             st.finish_device_ms += float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms)
                             st.records_device_ms += rb.records_ms
+                            st.nm_device_ms += nm_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up

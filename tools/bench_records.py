@@ -15,6 +15,8 @@ For a chr20 window of --reads reads held in memory, JSON with
     run_bam_to_bam device_records against device_records + device_batch, three alternating runs each.
   - plo_part_start_dev and the first cut of part 1 of 2 of the window's file against plo_bam_open_range and its first window on the host
     (--part-out; this leg runs alone)
+  - plo_nm_dev on the window (--nm-out; this leg runs alone): nm_ms beside the window's lift, finish and records_ms event times, the bases
+    compared and the kernel's algorithmic bytes, and one device-to-device hipMemcpyAsync of that many bytes taken in the same process
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -26,6 +28,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --batch-out profiles/r09_batch_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --cut-out profiles/r10_cut_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --part-out profiles/r11_part_start.json
+    python tools/bench_records.py --reads 50000 --nm-out profiles/r12_nm_window.json
 """
 import argparse
 import ctypes as C
@@ -362,6 +365,75 @@ def batch_leg(a, win, index, cn, dev):
     return res, bool(same)
 
 
+def nm_leg(a, win, index, cn, rn, dev):
+    """ONE window: plo_nm_dev beside the window's lift, finish and records calls, and against a device-to-device copy of its algorithmic bytes"""
+    import numpy as np
+    import torch
+
+    from portello_amd import abi, api, build, devbatch
+
+    def arr(ptr, dtype, count):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype) if count else np.zeros(0, dtype)
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    lift_ms, fin_ms, nm_ms, rec_ms, rec_plain_ms = [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        out = eng.liftover_batch_dev(ddesc)
+        eng.compact_output_dev(out)
+        tm = eng.timing()
+        fo = eng.finish_batch_dev(ddesc, up.finish_in())
+        so = eng.sa_segments_dev(sa_in)
+        plain = eng.records_build_dev(ddesc, rin)  # (no NM result on the context yet: today's bytes)
+        plain_bytes, plain_ms = int(plain.n_bytes), float(plain.records_ms)
+        no = eng.nm_dev(ddesc)
+        ro = eng.records_build_dev(ddesc, rin)
+        if k >= a.warmup:
+            lift_ms.append(float(tm.total_ms))
+            fin_ms.append(float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms))
+            nm_ms.append(float(no.nm_ms))
+            rec_ms.append(float(ro.records_ms))
+            rec_plain_ms.append(plain_ms)
+    lift = devbatch.download(eng, out)
+    lifted = np.flatnonzero(lift.item_status == abi.ITEM_LIFTED)
+    l_seq = arr(b.read_seq_len, np.uint32, int(b.n_reads))[arr(b.seg_read, np.uint32, int(b.n_segs))[lift.item_seg[lifted]]].astype(np.int64)
+    ops = lift.cigar.astype(np.int64)
+    ref_adv = np.where(np.isin(ops & 15, (0, 2, 3, 7, 8)), ops >> 4, 0)
+    csum = np.concatenate([[0], np.cumsum(ref_adv)])
+    o0 = lift.item_cigar_off[lifted].astype(np.int64)
+    o1 = o0 + lift.item_cigar_len[lifted]
+    ref_span = csum[o1] - csum[o0]
+    algo = int(((l_seq + 1) // 2).sum() + ref_span.sum() + 4 * int(lift.item_cigar_len[lifted].sum()))
+    same = int(ro.n_bytes) == plain_bytes + 7 * len(lifted) and int(no.n_items) == lift.n_items
+    # the yardstick: one device-to-device hipMemcpyAsync of that many bytes, in this process
+    src, dst = torch.empty(algo, dtype=torch.uint8, device=dev), torch.empty(algo, dtype=torch.uint8, device=dev)
+    src.zero_()
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "items": int(lift.n_items), "lifted_items": int(len(lifted)), "cigar_ops_of_lifted": int(lift.item_cigar_len[lifted].sum()),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "records_grow_by_7_per_lifted": bool(same), "n_cmp_bases": int(no.n_cmp_bases), "algorithmic_bytes": algo,
+           "algorithmic_bytes_note": "(l_seq + 1) / 2 + reference span + 4 x ops over the lifted items", "nm_ms": stats(nm_ms), "lift_ms": stats(lift_ms),
+           "finish_sa_ms": stats(fin_ms), "records_ms": stats(rec_ms), "records_without_nm_ms": stats(rec_plain_ms), "d2d_copy_same_bytes_ms": stats(d2d),
+           "nm_gbs": algo / med(nm_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * algo / med(d2d) / 1e6, "nm_over_d2d_copy_time": med(nm_ms) / med(d2d)}
+    return res, bool(same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -377,6 +449,7 @@ def main():
     ap.add_argument("--batch-out", default="", help="run the batch-construction leg (plo_batch_build_dev) alone and write its JSON there")
     ap.add_argument("--cut-out", default="", help="run the input leg (plo_bgzf_inflate_dev + plo_window_cut_dev) alone and write its JSON there")
     ap.add_argument("--part-out", default="", help="run the part leg (plo_part_start_dev and the first cut of part 1 of 2 against plo_bam_open_range) alone and write its JSON there")
+    ap.add_argument("--nm-out", default="", help="run the NM leg (plo_nm_dev beside the window's lift, finish and records times, against a device-to-device copy) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -418,6 +491,15 @@ def main():
             with open(a.cut_out, "w") as fh:
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
+    if a.nm_out:
+        nres, ok = nm_leg(a, win, index, cn, rn, dev)
+        win.close()
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.nm_out)), exist_ok=True)
+        with open(a.nm_out, "w") as fh:
+            fh.write(json.dumps(nres, indent=1) + "\n")
+        print(json.dumps(nres))
         sys.exit(0 if ok else 1)
     if a.batch_out:
         bres, ok = batch_leg(a, win, index, cn, dev)
