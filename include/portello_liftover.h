@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 12 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev) */
+#define PLO_API_VERSION 13 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -407,6 +407,38 @@ typedef struct plo_nm_out {
 } plo_nm_out;
 
 plo_status plo_nm_dev(plo_ctx *ctx, const plo_batch_in *in, plo_nm_out *out);
+
+/* ---- MD:Z of the lifted records (device-resident, opt-in) ---------------------------------------------------------
+ * calmd's second output.  clone_record does not cut MD: a source record that carries one (against the contig) leaves with it unchanged,
+ * and it is wrong on the reference.  plo_md_dev writes the text for every item with status PLO_ITEM_LIFTED from the same inputs as
+ * plo_nm_dev.  The rule is bam_fillmd1_core's (bam_md.c): a counter u of matched bases starts at 0; M / = / X go base by base, a pair
+ * matches exactly as for plo_nm_dev; a match does ++u, a mismatch writes u in decimal (also 0), the reference letter, u = 0.  A D of
+ * length > 0 writes u (also 0), '^', its reference letters, u = 0 (two in a row: ...^AC0^GTT...).  I, S, N, H, P write nothing and keep u.
+ * At the end u is written, so the text of a LIFTED item is never empty ("0" without compared bases and deletions).  Ops of length 0 are
+ * skipped: calmd would write an empty '^' for 0D, the lift never emits one.  The reference letter is the chrom_seq byte: A..Z as it
+ * is, a..z upper-cased (calmd's toupper), any other byte 'N', which keeps the text inside [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*.  The letters
+ * of the text (those behind '^' too) plus the I lengths are plo_nm_dev's NM of the item.
+ * Call order and refusals are plo_nm_dev's: after plo_liftover_batch_dev (+ plo_compact_output_dev) and plo_finish_batch_dev on the same
+ * context and batch; out of order, sparse or ASCII bases, an index without chrom_seq -> PLO_ERR_INVALID_ARG; a CIGAR past the chromosome
+ * or the read -> PLO_ERR_RANGE by the same check on the device, err_item the LOWEST such item, no result handed out.  The call is
+ * independent of plo_nm_dev: either alone, both in either order, neither drops the other's result.
+ * While the context holds a result, plo_records_build_dev writes 'M','D','Z' + text + NUL into every lifted record, behind ZM:C, behind
+ * NM:i when that is written too (calmd appends NM, then MD), in front of SA:Z / CG:B,I, and cuts the FIRST field tagged MD of the source
+ * record, whatever its type, from the lifted records.  The unmapped copy gets no MD and keeps its source aux bytes.  Without a result every
+ * byte is as before, a stale source MD included.  The result is dropped by the context's next plo_liftover_batch* (and
+ * plo_finish_batch_dev) call.  Host builders write no MD.  Two passes over the same bytes (lengths, then text) with the 64-bit scan of the
+ * lengths between them; TWO waits: one for the total size, one behind the emit.  Outputs are owned by the context, valid until its next
+ * plo_liftover_batch* call. */
+typedef struct plo_md_out {
+    uint32_t n_items;
+    const uint64_t *item_md_off;  /* [n_items + 1] device; an item that is not LIFTED has length 0 */
+    const uint8_t *md_text;       /* device; the values side by side, no tag, no NUL */
+    uint64_t md_bytes;
+    uint32_t err_item;            /* PLO_ERR_RANGE: lowest offending item, UINT32_MAX otherwise */
+    float md_ms;                  /* HIP-event time of the call's kernels */
+} plo_md_out;
+
+plo_status plo_md_dev(plo_ctx *ctx, const plo_batch_in *in, plo_md_out *out);
 
 /* ---- BGZF blocks (device-resident) ------------------------------------------------------------------------------
  * Cuts the n_bytes at `bytes` -- any device buffer, typically plo_records_out::bytes -- into payloads of 0xff00 bytes (htslib's

@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 12  # include/portello_liftover.h
+PLO_API_VERSION = 13  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -185,6 +185,10 @@ class PloRecordsOut(C.Structure):
 
 class PloNmOut(C.Structure):
     _fields_ = [("n_items", C.c_uint32), ("item_nm", _u32p), ("n_cmp_bases", C.c_uint64), ("err_item", C.c_uint32), ("nm_ms", C.c_float)]
+
+
+class PloMdOut(C.Structure):
+    _fields_ = [("n_items", C.c_uint32), ("item_md_off", _u64p), ("md_text", _u8p), ("md_bytes", C.c_uint64), ("err_item", C.c_uint32), ("md_ms", C.c_float)]
 
 
 class PloBgzfOut(C.Structure):

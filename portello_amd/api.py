@@ -78,6 +78,8 @@ def load_library(path: Optional[str] = None):
     L.plo_finish_batch_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloFinishIn), C.POINTER(abi.PloFinishOut)]
     L.plo_nm_dev.restype = C.c_int
     L.plo_nm_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloNmOut)]
+    L.plo_md_dev.restype = C.c_int
+    L.plo_md_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloMdOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_bgzf_inflate_dev.restype = C.c_int
@@ -249,6 +251,21 @@ class Engine:
         if st != abi.PLO_OK:
             msg = self.lib.plo_last_error(self.handle)
             e = PortelloError(st, f"plo_nm_dev: {msg.decode() if msg else ''}")
+            e.err_item = int(out.err_item)
+            raise e
+        return out
+
+    def md_dev(self, desc: abi.PloBatchIn) -> abi.PloMdOut:
+        """MD:Z of every lifted item of the batch this context has just lifted, compacted and finished (plo_md_dev): calmd's text of the
+        output record against the index's chromosomes, the items' values side by side with their offsets; device pointers out.  While the
+        result stands (until the next lift call), records_build_dev writes MD:Z into every lifted record and cuts the source's MD.
+        Independent of nm_dev.  A CIGAR that leaves its chromosome or its read raises PortelloError with status PLO_ERR_RANGE and the
+        lowest such item in `err_item`."""
+        out = abi.PloMdOut()
+        st = self.lib.plo_md_dev(self.handle, C.byref(desc), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_md_dev: {msg.decode() if msg else ''}")
             e.err_item = int(out.err_item)
             raise e
         return out

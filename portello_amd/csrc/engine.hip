@@ -42,6 +42,7 @@
 #include "records_core.hpp"
 #include "batch_core.hpp"
 #include "nm_core.hpp"
+#include "md_core.hpp"
 #include "window_core.hpp"
 #include "bgzf_walk.hpp"
 #include "index_pack.hpp"
@@ -1315,6 +1316,11 @@ __global__ __launch_bounds__(256) void k_rec_emit(DevBatch bt, DevWork wk, DevRe
 // persistent waves, items by ticket.  HBM-bound by design: per lifted item l_seq / 2 bytes of bases, ~l_seq bytes of reference, 4 x ops
 __global__ __launch_bounds__(256) void k_nm(DevBatch bt, DevWork wk, DevNm d) { nm_items(bt, wk, d); }
 
+// ---- MD:Z of the lifted records (md_core.hpp) ------------------------------------------------------------------------------
+// the same persistent waves, twice over the same bytes: the lengths of the items' texts, then (behind the 64-bit scan) the texts
+__global__ __launch_bounds__(256) void k_md_count(DevBatch bt, DevWork wk, DevMd d) { md_items<false>(bt, wk, d); }
+__global__ __launch_bounds__(256) void k_md_emit(DevBatch bt, DevWork wk, DevMd d) { md_items<true>(bt, wk, d); }
+
 // ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
 // the label table: a thread per contig name
 __global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
@@ -1606,6 +1612,10 @@ struct plo_ctx {
     DevBuf nm_out, nm_blk;
     HostBuf h_nm;
     hipEvent_t nev[2] = {nullptr, nullptr};
+    bool have_md = false;  // plo_md_dev's result of the current batch: plo_records_build_dev writes MD:Z from it and cuts the source's MD; dropped like have_nm
+    DevBuf md_len, md_off, md_partial, md_text, md_blk;
+    HostBuf h_md;
+    hipEvent_t mev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1963,7 +1973,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
-                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk,
+                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1973,7 +1983,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1991,6 +2001,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->iev[i]) (void)hipEventDestroy(c->iev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->nev[i]) (void)hipEventDestroy(c->nev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->mev[i]) (void)hipEventDestroy(c->mev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -2155,6 +2167,7 @@ plo_status plo_liftover_batch_dev(plo_ctx *c, const plo_batch_in *in, uint32_t s
     memset(out, 0, sizeof(*out));
     c->err.clear();
     c->have_nm = false;
+    c->have_md = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     if (in->n_segs && (!in->seg_read || !in->seg_contig || !in->seg_pos || !in->seg_is_fwd_strand || !in->seg_cigar_off)) {
         c->err = "plo_batch_in: NULL segment array";
@@ -3025,6 +3038,7 @@ plo_status plo_finish_batch_dev(plo_ctx *c, const plo_batch_in *in, const plo_fi
     c->have_finish = false;
     c->have_sa = false;
     c->have_nm = false;
+    c->have_md = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     hipStream_t st = c->stream;
     for (int i = 0; i < 3; ++i)
@@ -3252,6 +3266,8 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     d.sa_off = c->sa_off.as<uint32_t>();
     d.sa_text = c->sa_text.as<uint8_t>();
     d.item_nm = c->have_nm ? c->nm_out.as<uint32_t>() : nullptr;
+    d.item_md_off = c->have_md ? c->md_off.as<uint64_t>() : nullptr;
+    d.md_text = c->have_md ? c->md_text.as<uint8_t>() : nullptr;
     d.cs_is_fwd = c->ix->d.cs_is_fwd;
     d.contig_seg_off = c->ix->d.contig_seg_off;
     d.plan = c->r_plan.as<uint32_t>();
@@ -3389,6 +3405,109 @@ plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
     out->item_nm = d.item_nm;
     out->n_cmp_bases = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
     c->have_nm = true;
+    return PLO_OK;
+}
+
+// MD:Z of every lifted item (md_core.hpp): k_md_count, the 64-bit scan of the lengths, a wait for the total and the refusal, k_md_emit, a
+// wait behind it (the event time).  Two waits.
+plo_status plo_md_dev(plo_ctx *c, const plo_batch_in *in, plo_md_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_item = UINT32_MAX;
+    c->err.clear();
+    c->have_md = false;
+    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
+        c->err = "plo_md_dev: the batch came with sparse or ASCII bases; MD is written from complete BAM 4-bit bases (PLO_SEQ_BAM4)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
+        c->err = "plo_md_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_finish) {
+        c->err = "plo_md_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevIndex &ix = c->ix->d;
+    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
+        c->err = "plo_md_dev: the index has no chrom_seq";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevWork &wk = c->last_wk;
+    const DevBatch &bt = c->last_bt;
+    const uint32_t n = wk.n_items;
+    if (n > (uint32_t)NM_NO_ITEM) {
+        c->err = "plo_md_dev: more than 2^31 - 1 items in one batch";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->mev[i]) HIP_TRY(c, hipEventCreate(&c->mev[i]));
+    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    HIP_TRY(c, c->md_len.ensure((size_t)std::max(1u, n) * 8));
+    HIP_TRY(c, c->md_off.ensure(((size_t)n + 1) * 8));
+    HIP_TRY(c, c->md_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->md_blk.ensure(16));  // err_item, the count pass's ticket, the emit pass's ticket
+    HIP_TRY(c, c->h_md.ensure(32));
+    DevMd d;
+    memset(&d, 0, sizeof(d));
+    d.item_seq_off = c->f_isoff.as<uint64_t>();
+    d.rev_seq = c->f_rseq.as<uint8_t>();
+    d.chrom_seq = ix.chrom_seq;
+    d.chrom_len = ix.chrom_len;
+    d.n_chroms = ix.n_chroms;
+    d.item_len = c->md_len.as<unsigned long long>();
+    d.err_item = c->md_blk.as<int>();
+    d.ticket = c->md_blk.as<unsigned>() + 1;
+    unsigned long long *off = c->md_off.as<unsigned long long>();
+    uint32_t *h = c->h_md.as<uint32_t>();
+    h[0] = (uint32_t)NM_NO_ITEM;
+    h[1] = h[2] = h[3] = 0;
+    h[4] = h[5] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->md_blk.p, h, 16, hipMemcpyHostToDevice, st));
+    // as many waves as stay resident (k_nm's grid: five workgroups of four per CU at up to 96 VGPRs), never more than items
+    const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
+    HIP_TRY(c, hipEventRecord(c->mev[0], st));
+    if (n) {
+        hipLaunchKernelGGL(k_md_count, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, c->md_partial.as<unsigned long long>());
+        hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->md_partial.as<unsigned long long>(), n, nb, off);
+        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, (const unsigned long long *)c->md_partial.as<unsigned long long>(), off);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h + 4, off + n, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(c->md_off.p, 0, 8, st));
+    }
+    HIP_TRY(c, hipEventRecord(c->mev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->md_blk.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)NM_NO_ITEM) {
+        out->err_item = h[0];
+        c->err = "plo_md_dev: the CIGAR of item " + std::to_string(h[0]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no MD is handed out";
+        return PLO_ERR_RANGE;
+    }
+    const uint64_t total = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
+    HIP_TRY(c, c->md_text.ensure((size_t)total + 16));
+    d.item_md_off = off;
+    d.md_text = c->md_text.as<uint8_t>();
+    d.ticket = c->md_blk.as<unsigned>() + 2;
+    HIP_TRY(c, hipEventRecord(c->mev[2], st));
+    if (n) {
+        hipLaunchKernelGGL(k_md_emit, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->mev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, c->mev[0], c->mev[1]);
+    (void)hipEventElapsedTime(&b, c->mev[2], c->mev[3]);
+    out->md_ms = a + b;
+    out->n_items = n;
+    out->item_md_off = c->md_off.as<uint64_t>();
+    out->md_text = d.md_text;
+    out->md_bytes = total;
+    c->have_md = true;
     return PLO_OK;
 }
 

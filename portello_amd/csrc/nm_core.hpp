@@ -38,8 +38,8 @@ struct DevNm {
     unsigned *ticket;               // [1] next item
 };
 
-// mismatches of the four bases whose codes are the bytes of `cd` against the four reference bytes `rf`
-PLO_DEV uint32_t nm_mismatch4(uint32_t cd, uint32_t rf) {
+// the four bases whose codes are the bytes of `cd` against the four reference bytes `rf`: 0x80 in byte k where pair k mismatches
+PLO_DEV uint32_t nm_mismask4(uint32_t cd, uint32_t rf) {
     const uint32_t T0 = 0x4D43413Du, T1 = 0x56535247u, T2 = 0x48595754u, T3 = 0x4E42444Bu;  // "=ACM" "GRSV" "TWYH" "KDBN"
     const uint32_t idx = cd & 0x07070707u;
     const uint32_t lo = wv::perm_bytes(T1, T0, idx), hi = wv::perm_bytes(T3, T2, idx);
@@ -48,8 +48,12 @@ PLO_DEV uint32_t nm_mismatch4(uint32_t cd, uint32_t rf) {
     const uint32_t differs = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
     const uint32_t is15 = ((cd + 0x01010101u) & 0x10101010u) << 3;
     const uint32_t not0 = (cd + 0x7f7f7f7fu) & 0x80808080u;
-    return (uint32_t)__builtin_popcount((differs | is15) & not0);
+    return (differs | is15) & not0;
 }
+// their number
+PLO_DEV uint32_t nm_mismatch4(uint32_t cd, uint32_t rf) { return (uint32_t)__builtin_popcount(nm_mismask4(cd, rf)); }
+// the 0x80 of byte k as bit k (the partial products of the multiplication meet in no bit)
+PLO_DEV uint32_t nm_mask_bits(uint32_t m) { return ((m >> 7) * 0x10204080u) >> 28; }
 
 // one pair, the rule as it is stated
 PLO_DEV uint32_t nm_mismatch1(unsigned c1, unsigned ch) {
@@ -60,8 +64,9 @@ PLO_DEV uint32_t nm_mismatch1(unsigned c1, unsigned ch) {
 }
 
 // piece j of a match op: reference bytes [fa, fa + len) (an address), read bases from rd on; `seq` = the record's 4-bit bases,
-// [seq_lo, seq_hi) their addresses
-PLO_DEV uint32_t nm_piece(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi, uintptr_t fa, uint32_t len, unsigned long long rd, uint32_t j) {
+// [seq_lo, seq_hi) their addresses.  MASK false: the piece's mismatches (k_nm); true: bit k set where its base k mismatches (md_core.hpp)
+template <bool MASK>
+PLO_DEV uint32_t nm_piece_t(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi, uintptr_t fa, uint32_t len, unsigned long long rd, uint32_t j) {
     uintptr_t s = (fa & ~(uintptr_t)15) + 16u * (uintptr_t)j, e = s + 16;
     if (s < fa) s = fa;
     if (e > fa + len) e = fa + len;
@@ -80,8 +85,12 @@ PLO_DEV uint32_t nm_piece(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi
             const bool odd = (rp & 1u) != 0;
             const uint64_t a = odd ? lo0 : hi0, bb = odd ? hi1 : lo0;
             const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)bb, b1 = (uint32_t)(bb >> 32);
-            return nm_mismatch4(wv::perm_bytes(a0, b0, 0x01050004u), (uint32_t)r0) + nm_mismatch4(wv::perm_bytes(a0, b0, 0x03070206u), (uint32_t)(r0 >> 32)) +
-                   nm_mismatch4(wv::perm_bytes(a1, b1, 0x01050004u), (uint32_t)r1) + nm_mismatch4(wv::perm_bytes(a1, b1, 0x03070206u), (uint32_t)(r1 >> 32));
+            const uint32_t c0 = wv::perm_bytes(a0, b0, 0x01050004u), c1 = wv::perm_bytes(a0, b0, 0x03070206u);
+            const uint32_t c2 = wv::perm_bytes(a1, b1, 0x01050004u), c3 = wv::perm_bytes(a1, b1, 0x03070206u);
+            if (MASK)
+                return nm_mask_bits(nm_mismask4(c0, (uint32_t)r0)) | (nm_mask_bits(nm_mismask4(c1, (uint32_t)(r0 >> 32))) << 4) |
+                       (nm_mask_bits(nm_mismask4(c2, (uint32_t)r1)) << 8) | (nm_mask_bits(nm_mismask4(c3, (uint32_t)(r1 >> 32))) << 12);
+            return nm_mismatch4(c0, (uint32_t)r0) + nm_mismatch4(c1, (uint32_t)(r0 >> 32)) + nm_mismatch4(c2, (uint32_t)r1) + nm_mismatch4(c3, (uint32_t)(r1 >> 32));
         }
     }
     uint32_t n = 0;
@@ -89,9 +98,13 @@ PLO_DEV uint32_t nm_piece(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi
     for (uint32_t k = 0; k < (uint32_t)(e - s); ++k) {
         const unsigned long long p = rp + k;
         const unsigned byte = seq[p >> 1];
-        n += nm_mismatch1((p & 1u) ? (byte & 15u) : (byte >> 4), rf[k]);
+        const uint32_t m = nm_mismatch1((p & 1u) ? (byte & 15u) : (byte >> 4), rf[k]);
+        n += MASK ? m << k : m;
     }
     return n;
+}
+PLO_DEV uint32_t nm_piece(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi, uintptr_t fa, uint32_t len, unsigned long long rd, uint32_t j) {
+    return nm_piece_t<false>(seq, seq_lo, seq_hi, fa, len, rd, j);
 }
 
 PLO_DEV void nm_refuse(const DevNm &d, uint32_t i) {

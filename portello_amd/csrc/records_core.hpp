@@ -4,10 +4,12 @@
 // as htslib's bam_write1 does (CG:B,I beyond 65535 CIGAR ops).  Everything but the layout is already on the device: the lift result
 // (DevWork), the finishing (flags, bin, reference end, reversed bases and qualities: finish_core.hpp) and the SA segments.
 //   plan  (a wave per read):  bounds of the source record, the aux walk of aux_field_len / aux_find / plan_aux / has_cg_cigar
-//                             (bam_internal.hpp, bam_host.cpp) -> at most five cuts sorted by offset, the kept length, the read's bytes
+//                             (bam_internal.hpp, bam_host.cpp) -> at most six cuts sorted by offset, the kept length, the read's bytes
 //   scan  (waves):            exclusive 64-bit scan of the reads' bytes and record counts
 //   emit  (a workgroup per read): every byte of the read's records, the bulk as aligned 16-byte stores
-// With DevRecords::item_nm (nm_core.hpp) every lifted record gets NM:i behind ZM:C; that is the one difference to the host builder.
+// With DevRecords::item_nm (nm_core.hpp) every lifted record gets NM:i behind ZM:C.  With DevRecords::item_md_off / md_text (md_core.hpp) it
+// gets MD:Z behind that (calmd appends NM, then MD), and the first field tagged MD of the source record, whatever its type, is cut from the
+// lifted records (the sixth cut; an unmapped copy keeps it).  Those are the two differences to the host builder.
 // The same functions run under the CPU emulator (tests/emu/emu_records.cpp).
 #pragma once
 #include <plo_wave.hpp>
@@ -19,7 +21,7 @@
 namespace plo {
 
 // per-read plan: REC_PLAN_WORDS dwords
-enum { RP_NCUT = 0, RP_KEPT = 1, RP_CUT_OFF = 2, RP_CUT_LEN = 7, RP_AUX_OFF = 12, RP_BLOCK = 13, REC_PLAN_WORDS = 16 };
+enum { RP_NCUT = 0, RP_KEPT = 1, RP_CUT_OFF = 2, RP_CUT_LEN = 8, RP_AUX_OFF = 14, RP_BLOCK = 15, REC_PLAN_WORDS = 16, REC_MAX_CUTS = 6 };
 // d.err[k]: number of reads that failed check k
 enum { REC_ERR_OFFSET = 0,  // read_rec_off points outside `records`
        REC_ERR_BLOCK = 1,   // block_size runs past the end of `records` (or is below the 32 fixed bytes)
@@ -47,6 +49,8 @@ struct DevRecords {
     const uint32_t *sa_off;
     const uint8_t *sa_text;
     const uint32_t *item_nm;  // the context's plo_nm_dev result: NM:i behind ZM:C of every lifted record; NULL: no NM, the host builder's bytes
+    const uint64_t *item_md_off;  // the context's plo_md_dev result: MD:Z behind ZM:C / NM:i of every lifted record, the source's first MD cut; NULL: neither
+    const uint8_t *md_text;
     // the index: strand of the contig segments (PS suffix)
     const uint8_t *cs_is_fwd;
     const uint32_t *contig_seg_off;
@@ -114,7 +118,8 @@ PLO_DEV unsigned long long rec_lifted_size(const DevBatch &bt, const DevWork &wk
     const uint32_t contig = bt.seg_contig[wk.item_seg[i]];
     unsigned long long sz = base + (nc <= 0xffffu ? 4ull * nc : 8ull + 8ull + 4ull * nc);  // bam_write1: placeholder + CG:B,I
     sz += 3ull + (d.contig_name_off[contig + 1] - d.contig_name_off[contig]) + 6u + dec_digits(wk.item_cseg[i]) + 1u + 1u;  // PS:Z{contig}_split{n}{+|-}\0
-    return sz + 4 + (d.item_nm ? 7u : 0u);  // ZM:C, NM:i
+    sz += 4 + (d.item_nm ? 7u : 0u);  // ZM:C, NM:i
+    return d.item_md_off ? sz + 3ull + (d.item_md_off[i + 1] - d.item_md_off[i]) + 1 : sz;  // MD:Z{text}\0
 }
 
 // plan + size of read r by one wave (every lane computes the same values; lane 0 stores them)
@@ -154,7 +159,10 @@ PLO_DEV void records_plan_read(const DevBatch &bt, const DevWork &wk, const DevR
         return;
     }
     // the walk of plan_aux (bam_host.cpp:736-767): the first NM, SA, PS, ZM are cut, the first CG when it is a B,I array and the stored
-    // CIGAR is the <l_seq>S<n>N placeholder (has_cg_cigar :725-735); nothing behind the first malformed field is looked at
+    // CIGAR is the <l_seq>S<n>N placeholder (has_cg_cigar :725-735); nothing behind the first malformed field is looked at.  With an MD
+    // result the first MD of a read with lifted records is cut too (the unmapped copy of a read without keeps its aux bytes)
+    const uint32_t nl = d.read_n_lifted[r];
+    const bool cut_md = d.item_md_off != nullptr && nl > 0;
     const uint8_t *e = p + bs;
     const uint8_t *a = p + aux_off;
     unsigned seen = 0;
@@ -163,10 +171,10 @@ PLO_DEV void records_plan_read(const DevBatch &bt, const DevWork &wk, const DevR
         const unsigned long long n = aux_field_len_wave(a, e);
         if (!n) break;
         const unsigned t0 = a[0], t1 = a[1];
-        const int k = (t0 == 'N' && t1 == 'M') ? 0 : (t0 == 'S' && t1 == 'A') ? 1 : (t0 == 'P' && t1 == 'S') ? 2 : (t0 == 'Z' && t1 == 'M') ? 3 : (t0 == 'C' && t1 == 'G') ? 4 : -1;
+        const int k = (t0 == 'N' && t1 == 'M') ? 0 : (t0 == 'S' && t1 == 'A') ? 1 : (t0 == 'P' && t1 == 'S') ? 2 : (t0 == 'Z' && t1 == 'M') ? 3 : (t0 == 'C' && t1 == 'G') ? 4 : (cut_md && t0 == 'M' && t1 == 'D') ? 5 : -1;
         if (k >= 0 && !((seen >> k) & 1u)) {
             seen |= 1u << k;
-            if (k < 4) {
+            if (k != 4) {
                 if (lane0) {
                     pl[RP_CUT_OFF + n_cut] = (uint32_t)(a - p);
                     pl[RP_CUT_LEN + n_cut] = (uint32_t)n;
@@ -203,7 +211,6 @@ PLO_DEV void records_plan_read(const DevBatch &bt, const DevWork &wk, const DevR
     const uint32_t kept = (uint32_t)(bs - aux_off) - cut_total;
     // sizes (records_build pass 1)
     const unsigned long long base = 4ull + 32 + lq + ((unsigned long long)lseq + 1) / 2 + lseq + kept;
-    const uint32_t nl = d.read_n_lifted[r];
     unsigned long long bytes = 0, nrec = 0;
     if (nl == 0) {
         if (!d.is_target_region) {  // unmapped copy :321-334
@@ -461,6 +468,17 @@ PLO_DEV void records_emit_read(const DevBatch &bt, const DevWork &wk, const DevR
             }
         }
         q += 3ull + cnl + 6 + dg + 2 + 4 + (d.item_nm ? 7u : 0u);
+        if (d.item_md_off) {  // MD:Z behind NM:i, the order calmd appends them in
+            const unsigned long long ml = d.item_md_off[i + 1] - d.item_md_off[i];
+            if (tid == 0) {
+                q[0] = 'M';
+                q[1] = 'D';
+                q[2] = 'Z';
+                q[3 + ml] = 0;
+            }
+            copy_bytes(q + 3, d.md_text + d.item_md_off[i], 0, ml, tid, nt);  // (a short text: bytewise, and no further instance of the 16-byte copy in the kernel)
+            q += 3ull + ml + 1;
+        }
         if (nl > 1) {  // SA:Z: the segments of the read's other records, in record order (:352-364)
             if (tid == 0) {
                 q[0] = 'S';

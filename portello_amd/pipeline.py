@@ -71,6 +71,7 @@ class PipelineStats:
     cut_device_ms: float = 0.0      # device_input: HIP-event time of plo_window_cut_dev (guess, walk, resolve, scans, find, emit)
     part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
     nm_device_ms: float = 0.0  # emit_nm: HIP-event time of plo_nm_dev (NM:i of the lifted records)
+    md_device_ms: float = 0.0  # emit_md: HIP-event time of plo_md_dev (MD:Z of the lifted records: count, scan, emit)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
@@ -85,8 +86,12 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
-                   device_input: bool = False, emit_nm: bool = False) -> PipelineStats:  # noqa: E501
-    """emit_nm (default off; needs device_records=True): every lifted record leaves with NM:i, calmd's edit distance against the
+                   device_input: bool = False, emit_nm: bool = False, emit_md: bool = False) -> PipelineStats:  # noqa: E501
+    """emit_md (default off; needs device_records=True): every lifted record leaves with MD:Z, calmd's text against the reference
+    chromosomes of the index (plo_md_dev between the finishing and plo_records_build_dev, which then writes the field behind ZM:C, behind
+    NM:i with emit_nm, and cuts the MD the source record carried); the unmapped copies get none and keep theirs.  Combines with emit_nm:
+    both on, the output needs no samtools calmd pass.  Off, every byte is what it was.
+    emit_nm (default off; needs device_records=True): every lifted record leaves with NM:i, calmd's edit distance against the
     reference chromosomes of the index (plo_nm_dev between the finishing and plo_records_build_dev, which then writes the field behind ZM:C);
     the unmapped copies get none.  Works with device_batch, device_input, device_bgzf and part / n_parts.  Off, every byte is what it was.
     device_input (default off; needs device_batch=True and so device_records=True; n_readers must be 1): the input's inflated
@@ -137,6 +142,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
     if emit_nm and not device_records:
         raise ValueError("emit_nm counts NM on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
+    if emit_md and not device_records:
+        raise ValueError("emit_md writes MD on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
     if device_input and not device_batch:
         raise ValueError("device_input hands plo_batch_build_dev windows that exist in device memory only: it needs device_batch=True (and device_records=True)")
     if device_input and int(n_readers) != 1:
@@ -320,6 +327,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             if emit_nm:
                                 nm_ms = float(eng.nm_dev(ddesc).nm_ms)
                                 marks.append(("nm", time.perf_counter()))
+                            md_ms = 0.0
+                            if emit_md:
+                                md_ms = float(eng.md_dev(ddesc).md_ms)
+                                marks.append(("md", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
                             if device_bgzf:
@@ -337,6 +348,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.finish_device_ms += float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms)
                             st.records_device_ms += rb.records_ms
                             st.nm_device_ms += nm_ms
+                            st.md_device_ms += md_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up

@@ -17,6 +17,9 @@ For a chr20 window of --reads reads held in memory, JSON with
     (--part-out; this leg runs alone)
   - plo_nm_dev on the window (--nm-out; this leg runs alone): nm_ms beside the window's lift, finish and records_ms event times, the bases
     compared and the kernel's algorithmic bytes, and one device-to-device hipMemcpyAsync of that many bytes taken in the same process
+  - plo_md_dev on the window (--md-out; runs alone or behind --nm-out): md_ms (count pass, scan, emit pass) beside the same window's nm_ms,
+    lift, finish and records_ms event times, the text's bytes and the two passes' algorithmic bytes, and one device-to-device
+    hipMemcpyAsync of that many bytes taken in the same process
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -29,6 +32,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --cut-out profiles/r10_cut_window.json --e2e-reads 180000
     python tools/bench_records.py --reads 50000 --part-out profiles/r11_part_start.json
     python tools/bench_records.py --reads 50000 --nm-out profiles/r12_nm_window.json
+    python tools/bench_records.py --reads 50000 --nm-out profiles/r13_nm_window.json --md-out profiles/r13_md_window.json
 """
 import argparse
 import ctypes as C
@@ -434,6 +438,85 @@ def nm_leg(a, win, index, cn, rn, dev):
     return res, bool(same)
 
 
+def md_leg(a, win, index, cn, rn, dev):
+    """ONE window: plo_md_dev beside the window's lift, finish, plo_nm_dev and records calls, and against a device-to-device copy of its
+    algorithmic bytes"""
+    import numpy as np
+    import torch
+
+    from portello_amd import abi, api, build, devbatch
+
+    def arr(ptr, dtype, count):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype) if count else np.zeros(0, dtype)
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    lift_ms, fin_ms, nm_ms, md_ms, md_wall_ms, rec_ms, rec_plain_ms = [], [], [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        out = eng.liftover_batch_dev(ddesc)
+        eng.compact_output_dev(out)
+        tm = eng.timing()
+        fo = eng.finish_batch_dev(ddesc, up.finish_in())
+        so = eng.sa_segments_dev(sa_in)
+        plain = eng.records_build_dev(ddesc, rin)  # (no NM or MD result on the context yet: the host builder's bytes)
+        plain_bytes, plain_ms = int(plain.n_bytes), float(plain.records_ms)
+        no = eng.nm_dev(ddesc)
+        t0 = time.perf_counter()
+        mo = eng.md_dev(ddesc)
+        t1 = time.perf_counter()
+        ro = eng.records_build_dev(ddesc, rin)
+        if k >= a.warmup:
+            lift_ms.append(float(tm.total_ms))
+            fin_ms.append(float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms))
+            nm_ms.append(float(no.nm_ms))
+            md_ms.append(float(mo.md_ms))
+            md_wall_ms.append((t1 - t0) * 1e3)
+            rec_ms.append(float(ro.records_ms))
+            rec_plain_ms.append(plain_ms)
+    lift = devbatch.download(eng, out)
+    lifted = np.flatnonzero(lift.item_status == abi.ITEM_LIFTED)
+    l_seq = arr(b.read_seq_len, np.uint32, int(b.n_reads))[arr(b.seg_read, np.uint32, int(b.n_segs))[lift.item_seg[lifted]]].astype(np.int64)
+    ops = lift.cigar.astype(np.int64)
+    ref_adv = np.where(np.isin(ops & 15, (0, 2, 3, 7, 8)), ops >> 4, 0)
+    csum = np.concatenate([[0], np.cumsum(ref_adv)])
+    o0 = lift.item_cigar_off[lifted].astype(np.int64)
+    o1 = o0 + lift.item_cigar_len[lifted]
+    ref_span = csum[o1] - csum[o0]
+    one_pass = int(((l_seq + 1) // 2).sum() + ref_span.sum() + 4 * int(lift.item_cigar_len[lifted].sum()))
+    md_bytes = int(mo.md_bytes)
+    algo = 2 * one_pass + md_bytes + 24 * int(lift.n_items)
+    # the source records of this window carry no MD: the records grow by NM:i (7) and MD:Z (3 + text + NUL) per lifted record
+    same = int(ro.n_bytes) == plain_bytes + (7 + 4) * len(lifted) + md_bytes and int(mo.n_items) == lift.n_items
+    src, dst = torch.empty(algo, dtype=torch.uint8, device=dev), torch.empty(algo, dtype=torch.uint8, device=dev)
+    src.zero_()
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "items": int(lift.n_items), "lifted_items": int(len(lifted)), "cigar_ops_of_lifted": int(lift.item_cigar_len[lifted].sum()),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "records_grow_by_nm_and_md": bool(same), "md_bytes": md_bytes, "algorithmic_bytes": algo,
+           "algorithmic_bytes_note": "2 x ((l_seq + 1) / 2 + reference span + 4 x ops over the lifted items) + the text + 24 x items (length out, offsets in and out)",
+           "md_ms": stats(md_ms), "md_call_wall_ms": stats(md_wall_ms), "nm_ms": stats(nm_ms), "lift_ms": stats(lift_ms), "finish_sa_ms": stats(fin_ms),
+           "records_ms": stats(rec_ms), "records_without_tags_ms": stats(rec_plain_ms), "d2d_copy_same_bytes_ms": stats(d2d),
+           "md_gbs": algo / med(md_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * algo / med(d2d) / 1e6, "md_over_d2d_copy_time": med(md_ms) / med(d2d),
+           "md_over_nm_time": med(md_ms) / med(nm_ms)}
+    return res, bool(same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -450,6 +533,7 @@ def main():
     ap.add_argument("--cut-out", default="", help="run the input leg (plo_bgzf_inflate_dev + plo_window_cut_dev) alone and write its JSON there")
     ap.add_argument("--part-out", default="", help="run the part leg (plo_part_start_dev and the first cut of part 1 of 2 against plo_bam_open_range) alone and write its JSON there")
     ap.add_argument("--nm-out", default="", help="run the NM leg (plo_nm_dev beside the window's lift, finish and records times, against a device-to-device copy) alone and write its JSON there")
+    ap.add_argument("--md-out", default="", help="run the MD leg (plo_md_dev beside the window's nm, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -492,14 +576,19 @@ def main():
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
         sys.exit(0 if ok else 1)
-    if a.nm_out:
-        nres, ok = nm_leg(a, win, index, cn, rn, dev)
+    if a.nm_out or a.md_out:
+        ok = True
+        for path_out, leg in ((a.nm_out, nm_leg), (a.md_out, md_leg)):
+            if not path_out:
+                continue
+            res, leg_ok = leg(a, win, index, cn, rn, dev)
+            ok = ok and leg_ok
+            os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
+            with open(path_out, "w") as fh:
+                fh.write(json.dumps(res, indent=1) + "\n")
+            print(json.dumps(res))
         win.close()
         rd.close()
-        os.makedirs(os.path.dirname(os.path.abspath(a.nm_out)), exist_ok=True)
-        with open(a.nm_out, "w") as fh:
-            fh.write(json.dumps(nres, indent=1) + "\n")
-        print(json.dumps(nres))
         sys.exit(0 if ok else 1)
     if a.batch_out:
         bres, ok = batch_leg(a, win, index, cn, dev)
