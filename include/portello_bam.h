@@ -172,6 +172,10 @@ plo_status plo_records_build_finished(plo_bam_window *w, const plo_batch_out *li
    @PG PN/ID/VN/CL.  Returns a malloc'ed NUL-terminated text (free with plo_bam_free_text). */
 char *plo_bam_output_header(uint32_t n_ref, const char *const *ref_names, const uint32_t *ref_lens, const char *program_name,
                             const char *program_version, const char *cmdline);
+/* The same text with @HD ... SO:<sort_order> (API version 14): "coordinate" for the runs of plo_records_sort_dev.  plo_bam_output_header
+   is this call with "unsorted". */
+char *plo_bam_output_header_so(uint32_t n_ref, const char *const *ref_names, const uint32_t *ref_lens, const char *program_name,
+                               const char *program_version, const char *cmdline, const char *sort_order);
 void plo_bam_free_text(char *text);
 
 /* level 0: BGZF blocks with stored (uncompressed) deflate data, what the reference selects for stdout (:67-71);
@@ -188,6 +192,18 @@ plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blocks, uint64
 plo_status plo_bam_writer_close(plo_bam_writer *w);
 /* bytes the writer has put into its file so far (header blocks included, an open partial block not) */
 uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w);
+
+/* k-way merge of coordinate-sorted BAM files into one (API version 14; host code, I/O bound).  Every run is walked record by record
+ * (a plain iterator: no record is classified or refused for what it is); the records go out ordered by (key, index of the path, order
+ * inside the path) with plo_records_sort_dev's key, n_ref taken from the header.  The output carries the runs' header and is written
+ * with the writer above at `level`.
+ *   n_paths == 0, a NULL path                                  PLO_ERR_INVALID_ARG
+ *   header text or @SQ list not identical in all runs          PLO_ERR_INVALID_ARG
+ *   a run whose keys decrease, a refID / pos outside the key   PLO_ERR_DATA (the message names the file and the record)
+ *   a run that cannot be opened, is truncated (no BGZF EOF block, a cut block or record) or corrupt      PLO_ERR_IO
+ * Every message names the run.  A merge that fails leaves no file at out_path (what it had written is removed).  Every run is read
+ * through a buffer of 4 MB refills, from the header on, so some hundred runs can be open at once. */
+plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_paths, const char *out_path, int level, int n_threads);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Phase 1: the contig->reference index from the assembly->reference BAM (scan_contig_bam,

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 13 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut) */
+#define PLO_API_VERSION 14 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -466,6 +466,44 @@ typedef struct plo_bgzf_out {
 } plo_bgzf_out;
 
 plo_status plo_bgzf_compress_dev(plo_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int level, plo_bgzf_out *out);
+
+/* ---- Coordinate-sorted records (device-resident, opt-in; API version 14) --------------------------------------------
+ * The records at `bytes` -- each prefixed by its block_size, typically plo_records_out::bytes / record_off -- copied in coordinate order
+ * into a buffer of the call's own.  The key of a record is
+ *     (uint64)(refID < 0 ? n_ref : refID) << 32 | (uint64)(pos + 1) << 1 | ((flag >> 4) & 1)
+ * with refID at +4, pos at +8 and flag at +18 from the block_size word, little-endian, and the records are ordered by the pair (key, input
+ * index): references in header order, then position, forward before reverse, refID -1 last, ties in input order.  The pair is unique, so
+ * the result is fully determined.
+ * Checked on the device before any byte is moved: record_off[0] == 0, record_off does not decrease and ends at n_bytes; every record is
+ * at least 36 bytes long and block_size + 4 is its length; refID lies in [-1, n_ref), pos in [-1, 2^31 - 2].  A record that breaks one of
+ * these -> PLO_ERR_INVALID_ARG, err_record the LOWEST such record, no result handed out, plo_last_error names the record and the field.
+ * n_records == 0 -> PLO_OK with empty outputs (record_off[0] == 0); NULL bytes or record_off with n_records > 0 -> PLO_ERR_INVALID_ARG.
+ * Buffers: the call's own, grown to the largest call and freed with the context: one copy of the window's bytes (n_bytes), two arrays of
+ * keys (2 x 8 n), two of indices (2 x 4 n), the lengths in input and in sorted order (2 x 8 n) and the offsets (8 (n + 1)): n_bytes +
+ * 48 n_records in all.  The input, the outputs of plo_records_build_dev and of every other call on the context stay valid and unchanged;
+ * the call's own outputs are valid until the context's next plo_records_sort_dev.  plo_bgzf_compress_dev takes out->bytes as it takes
+ * plo_records_out::bytes.  The call runs on the context's stream and returns when its kernels are through: ONE wait. */
+typedef struct plo_sort_in {
+    const uint8_t *bytes;         /* device: records, each prefixed by its block_size (plo_records_out::bytes, or any such buffer) */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    const uint64_t *record_off;   /* device [n_records + 1] */
+    uint32_t n_ref;               /* @SQ count of the output header: refID must lie in [-1, n_ref) */
+} plo_sort_in;
+
+typedef struct plo_sort_out {
+    const uint8_t *bytes;         /* device: the same records in sorted order, densely packed */
+    uint64_t n_bytes;             /* == in->n_bytes */
+    uint32_t n_records;
+    const uint64_t *record_off;   /* device [n_records + 1], of the sorted buffer */
+    const uint32_t *perm;         /* device [n_records]: sorted position j holds input record perm[j] */
+    const uint64_t *key;          /* device [n_records]: the sorted keys */
+    uint32_t n_mapped;            /* records with refID >= 0; the refID -1 tail begins at this sorted position */
+    uint32_t err_record;          /* PLO_ERR_INVALID_ARG from the device check: lowest offending input record, else UINT32_MAX */
+    float sort_ms;                /* HIP-event time of the call's kernels */
+} plo_sort_out;
+
+plo_status plo_records_sort_dev(plo_ctx *ctx, const plo_sort_in *in, plo_sort_out *out);
 
 /* ---- The liftover batch (device-resident) ------------------------------------------------------------------------
  * Builds the plo_batch_in / plo_finish_in of a window from its records as they stand in device memory: what plo_bam_window_batch_raw

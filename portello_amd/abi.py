@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 13  # include/portello_liftover.h
+PLO_API_VERSION = 14  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -189,6 +189,15 @@ class PloNmOut(C.Structure):
 
 class PloMdOut(C.Structure):
     _fields_ = [("n_items", C.c_uint32), ("item_md_off", _u64p), ("md_text", _u8p), ("md_bytes", C.c_uint64), ("err_item", C.c_uint32), ("md_ms", C.c_float)]
+
+
+class PloSortIn(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("n_ref", C.c_uint32)]
+
+
+class PloSortOut(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("perm", _u32p), ("key", _u64p),
+                ("n_mapped", C.c_uint32), ("err_record", C.c_uint32), ("sort_ms", C.c_float)]
 
 
 class PloBgzfOut(C.Structure):

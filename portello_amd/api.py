@@ -80,6 +80,8 @@ def load_library(path: Optional[str] = None):
     L.plo_nm_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloNmOut)]
     L.plo_md_dev.restype = C.c_int
     L.plo_md_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloMdOut)]
+    L.plo_records_sort_dev.restype = C.c_int
+    L.plo_records_sort_dev.argtypes = [vp, C.POINTER(abi.PloSortIn), C.POINTER(abi.PloSortOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_bgzf_inflate_dev.restype = C.c_int
@@ -275,6 +277,22 @@ class Engine:
         (plo_records_build_dev); device pointers in and out."""
         out = abi.PloRecordsOut()
         self._check(self.lib.plo_records_build_dev(self.handle, C.byref(desc), C.byref(rin), C.byref(out)), "plo_records_build_dev")
+        return out
+
+    def records_sort_dev(self, bytes_ptr, n_bytes: int, n_records: int, record_off_ptr, n_ref: int) -> abi.PloSortOut:
+        """The records at the DEVICE address `bytes_ptr` (plo_records_out::bytes / record_off, or any such buffer) copied in coordinate
+        order into a buffer of the context's own (plo_records_sort_dev): by (reference in header order, position, forward before reverse;
+        refID -1 last), ties in input order.  Device pointers out, valid until the engine's next records_sort_dev; the input stays
+        unchanged.  A record the device check refuses raises PortelloError with status PLO_ERR_INVALID_ARG and the lowest such record in
+        `err_record`."""
+        sin = abi.PloSortIn(C.cast(bytes_ptr, abi._u8p), int(n_bytes), int(n_records), C.cast(record_off_ptr, abi._u64p), int(n_ref))
+        out = abi.PloSortOut()
+        st = self.lib.plo_records_sort_dev(self.handle, C.byref(sin), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_records_sort_dev: {msg.decode() if msg else ''}")
+            e.err_record = int(out.err_record)
+            raise e
         return out
 
     def batch_build_dev(self, bin_: abi.PloBatchBuildIn) -> abi.PloBatchBuildOut:

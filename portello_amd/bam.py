@@ -77,6 +77,10 @@ def lib():
                                                  C.POINTER(PloRecordsParams), C.POINTER(PloRecordBuf)]
         L.plo_bam_output_header.restype = vp
         L.plo_bam_output_header.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.c_char_p]
+        L.plo_bam_output_header_so.restype = vp
+        L.plo_bam_output_header_so.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+        L.plo_bam_merge_runs.restype = C.c_int
+        L.plo_bam_merge_runs.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_int, C.c_int]
         L.plo_bam_free_text.restype = None
         L.plo_bam_free_text.argtypes = [vp]
         L.plo_bam_writer_open.restype = C.c_int
@@ -282,13 +286,26 @@ class BamReader:
             pass
 
 
-def output_header(ref_names: Sequence[str], ref_lens: Sequence[int], program_name="portello", program_version="0.6.1", cmdline="") -> str:
+def output_header(ref_names: Sequence[str], ref_lens: Sequence[int], program_name="portello", program_version="0.6.1", cmdline="",
+                  sort_order: str = "unsorted") -> str:
+    """the output files' header text; sort_order is the @HD SO: value ("coordinate" for the runs of sorted_runs, plo_bam_output_header_so)"""
     rn = _names(ref_names)
     rl = (C.c_uint32 * max(1, len(ref_lens)))(*[int(x) for x in ref_lens])
-    p = lib().plo_bam_output_header(len(ref_names), rn, rl, program_name.encode(), program_version.encode(), cmdline.encode())
+    if sort_order == "unsorted":
+        p = lib().plo_bam_output_header(len(ref_names), rn, rl, program_name.encode(), program_version.encode(), cmdline.encode())
+    else:
+        p = lib().plo_bam_output_header_so(len(ref_names), rn, rl, program_name.encode(), program_version.encode(), cmdline.encode(), sort_order.encode())
     s = C.string_at(p).decode()
     lib().plo_bam_free_text(p)
     return s
+
+
+def merge_runs(paths: Sequence[str], out_path: str, level: int = 0, n_threads: int = 4) -> None:
+    """plo_bam_merge_runs: the coordinate-sorted BAM files `paths` (the runs of run_bam_to_bam(sorted_runs=True), in
+    PipelineStats.out_paths order) merged into one, ordered by (key, index of the path, order inside the path).  Raises PortelloError:
+    PLO_ERR_INVALID_ARG (no path, differing headers), PLO_ERR_DATA (a run out of order), PLO_ERR_IO (a truncated or corrupt run)."""
+    arr = _names(list(paths))
+    _check(lib().plo_bam_merge_runs(arr, len(paths), out_path.encode(), int(level), int(n_threads)), "plo_bam_merge_runs")
 
 
 class BamWriter:

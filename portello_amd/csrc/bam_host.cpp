@@ -49,16 +49,22 @@ struct plo_bam_window {
     }
 };
 
+static plo_status bam_open_capped(const char *path, int n_threads, int device, size_t chunk_cap, plo_bam_reader **out);
+
 extern "C" {
 
 const char *plo_bam_last_error(void) { return g_bam_err.c_str(); }
 
 plo_status plo_bam_open(const char *path, int n_threads, plo_bam_reader **out) { return plo_bam_open_device(path, n_threads, -2, out); }
-plo_status plo_bam_open_device(const char *path, int n_threads, int device, plo_bam_reader **out) {
+plo_status plo_bam_open_device(const char *path, int n_threads, int device, plo_bam_reader **out) { return bam_open_capped(path, n_threads, device, 0, out); }
+}  // extern "C"
+// chunk_cap != 0: BgzfIn::chunk_cap, set before the first refill (the header read) so that no refill of this reader is larger
+static plo_status bam_open_capped(const char *path, int n_threads, int device, size_t chunk_cap, plo_bam_reader **out) {
     if (!path || !out) return PLO_ERR_INVALID_ARG;
     *out = nullptr;
     plo_bam_reader *r = new plo_bam_reader();
     r->threads = std::max(1, n_threads);
+    r->in.chunk_cap = chunk_cap;
     if (device >= 0) {  // BGZF blocks on that GPU from the first refill on (plo_bam_set_device_inflate)
         r->in.device = -2;
         r->in.dev_id = device;
@@ -99,6 +105,7 @@ plo_status plo_bam_open_device(const char *path, int n_threads, int device, plo_
     *out = r;
     return PLO_OK;
 }
+extern "C" {
 
 // One PART of a BAM file for one rank / worker (the reference gives every worker an IndexedReader and fetches its region,
 // src/worker_thread_data.rs:21-30, src/read_alignment_scanner.rs:382; here the split needs no index): the compressed file is cut at
@@ -1141,7 +1148,11 @@ extern "C" plo_status plo_records_build_finished(plo_bam_window *w, const plo_ba
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" char *plo_bam_output_header(uint32_t n_ref, const char *const *ref_names, const uint32_t *ref_lens, const char *program_name,
                                        const char *program_version, const char *cmdline) {
-    std::string t = "@HD\tVN:1.6\tSO:unsorted\n";
+    return plo_bam_output_header_so(n_ref, ref_names, ref_lens, program_name, program_version, cmdline, "unsorted");
+}
+extern "C" char *plo_bam_output_header_so(uint32_t n_ref, const char *const *ref_names, const uint32_t *ref_lens, const char *program_name,
+                                          const char *program_version, const char *cmdline, const char *sort_order) {
+    std::string t = std::string("@HD\tVN:1.6\tSO:") + (sort_order ? sort_order : "unsorted") + "\n";
     for (uint32_t i = 0; i < n_ref; ++i) t += std::string("@SQ\tSN:") + ref_names[i] + "\tLN:" + std::to_string(ref_lens[i]) + "\n";
     std::string pn = program_name ? program_name : "portello", pv = program_version ? program_version : "";
     t += "@PG\tPN:" + pn + "\tID:" + pn + "-" + pv + "\tVN:" + pv + "\tCL:" + (cmdline ? cmdline : "") + "\n";
@@ -1500,4 +1511,126 @@ extern "C" plo_status plo_bam_writer_close(plo_bam_writer *w) {
     ::close(w->fd);
     delete w;
     return st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k-way merge of coordinate-sorted runs (the windows of run_bam_to_bam(sorted_runs=True), plo_records_sort_dev's order)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+struct MergeRun {
+    plo_bam_reader *r = nullptr;
+    std::string path;
+    uint64_t n_read = 0;       // records taken so far
+    const uint8_t *rec = nullptr;  // the current record (block_size word first) inside the reader's buffer, NULL at the end
+    size_t len = 0;
+    uint64_t key = 0;
+    bool have_prev = false;
+    uint64_t prev_key = 0;
+};
+// the next record of the run: a plain walk over the inflated stream (no classification; the window reader refuses records a merge must pass)
+plo_status merge_next(MergeRun &m, uint32_t n_ref) {
+    BgzfIn &in = m.r->in;
+    if (m.rec) {
+        in.bpos += m.len;
+        m.rec = nullptr;
+    }
+    // a refill that fails (a cut or corrupt block, a CRC mismatch) is an I/O error of this run, whatever status the reader gave it
+    auto refill = [&](size_t want) {
+        if (in.avail() >= want || in.fill(want) == PLO_OK) return PLO_OK;
+        return fail(PLO_ERR_IO, m.path + ": " + g_bam_err);
+    };
+    plo_status st;
+    if ((st = refill(4)) != PLO_OK) return st;
+    if (in.avail() == 0) return PLO_OK;  // the end of the run
+    if (in.avail() < 4) return fail(PLO_ERR_IO, m.path + ": truncated BAM record");
+    const uint32_t bs = rd32(in.buf.data() + in.bpos);
+    if (bs < 32) return fail(PLO_ERR_IO, m.path + ": BAM record shorter than its fixed fields");
+    if ((st = refill(4 + (size_t)bs)) != PLO_OK) return st;
+    if (in.avail() < 4 + (size_t)bs) return fail(PLO_ERR_IO, m.path + ": truncated BAM record");
+    const uint8_t *p = in.buf.data() + in.bpos;
+    const int32_t ref = rdi32(p + 4), pos = rdi32(p + 8);
+    if (ref < -1 || (ref >= 0 && (uint32_t)ref >= n_ref) || pos < -1 || pos > 0x7ffffffe)
+        return fail(PLO_ERR_DATA, m.path + ": record " + std::to_string(m.n_read) + " has refID " + std::to_string(ref) + " / pos " + std::to_string(pos) +
+                                      " outside the header's references or a BAM position");
+    m.key = ((uint64_t)(ref < 0 ? n_ref : (uint32_t)ref) << 32) | ((uint64_t)(uint32_t)(pos + 1) << 1) | (uint64_t)((rd16(p + 18) >> 4) & 1u);
+    if (m.have_prev && m.key < m.prev_key)
+        return fail(PLO_ERR_DATA, m.path + ": record " + std::to_string(m.n_read) + " sorts in front of the record before it: the run is not in coordinate order");
+    m.have_prev = true;
+    m.prev_key = m.key;
+    m.rec = p;
+    m.len = 4 + (size_t)bs;
+    ++m.n_read;
+    return PLO_OK;
+}
+}  // namespace
+
+extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_paths, const char *out_path, int level, int n_threads) {
+    if (!paths || !n_paths || !out_path) return fail(PLO_ERR_INVALID_ARG, "plo_bam_merge_runs: at least one run and an output path are required");
+    std::vector<MergeRun> runs(n_paths);
+    plo_bam_writer *w = nullptr;
+    auto done = [&](plo_status s) {
+        const std::string keep = g_bam_err;
+        for (MergeRun &m : runs)
+            if (m.r) plo_bam_close(m.r);
+        if (w) {
+            const plo_status c = plo_bam_writer_close(w);
+            if (s == PLO_OK && c == PLO_OK) return c;
+            ::unlink(out_path);  // a failed merge leaves no file: what was written so far would read as a complete BAM
+            if (s == PLO_OK) return c;
+        }
+        if (s != PLO_OK) g_bam_err = keep;
+        return s;
+    };
+    static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t i = 0; i < n_paths; ++i) {
+        if (!paths[i]) return done(fail(PLO_ERR_INVALID_ARG, "plo_bam_merge_runs: NULL path"));
+        runs[i].path = paths[i];
+        plo_status st = bam_open_capped(paths[i], 1, -1, (size_t)4 << 20, &runs[i].r);  // all runs are open at once: 4 MB refills from the first on
+        if (st != PLO_OK) return done(fail(st == PLO_ERR_DATA ? PLO_ERR_DATA : PLO_ERR_IO, runs[i].path + ": " + g_bam_err));
+        BgzfIn &in = runs[i].r->in;
+        if (in.size < 28 || memcmp(in.map + in.size - 28, eof_block, 28) != 0) return done(fail(PLO_ERR_IO, runs[i].path + ": no BGZF EOF block at the end: the run is truncated"));
+        if (i && (runs[i].r->text != runs[0].r->text || runs[i].r->names != runs[0].r->names || runs[i].r->lens != runs[0].r->lens))
+            return done(fail(PLO_ERR_INVALID_ARG, runs[i].path + ": its header differs from the header of " + runs[0].path + "; runs of one merge carry the same header text and @SQ list"));
+    }
+    const plo_bam_reader *r0 = runs[0].r;
+    const uint32_t n_ref = (uint32_t)r0->names.size();
+    plo_status st = plo_bam_writer_open(out_path, r0->text.c_str(), n_ref, r0->name_ptrs.data(), r0->lens.data(), level, std::max(1, n_threads), &w);
+    if (st != PLO_OK) return done(st);
+    // a binary heap of run indices by (key, run): the order inside a run is the run's own
+    std::vector<uint32_t> heap;
+    auto before = [&](uint32_t a, uint32_t b) { return runs[a].key != runs[b].key ? runs[a].key < runs[b].key : a < b; };
+    auto sift_down = [&](size_t k) {
+        for (;;) {
+            size_t l = 2 * k + 1, rr = l + 1, m = k;
+            if (l < heap.size() && before(heap[l], heap[m])) m = l;
+            if (rr < heap.size() && before(heap[rr], heap[m])) m = rr;
+            if (m == k) return;
+            std::swap(heap[k], heap[m]);
+            k = m;
+        }
+    };
+    for (uint32_t i = 0; i < n_paths; ++i) {
+        if ((st = merge_next(runs[i], n_ref)) != PLO_OK) return done(st);
+        if (runs[i].rec) heap.push_back(i);
+    }
+    for (size_t k = heap.size() / 2; k-- > 0;) sift_down(k);
+    std::vector<uint8_t> pend;
+    const size_t flush_at = (size_t)8 << 20;
+    pend.reserve(flush_at + (1u << 20));
+    while (!heap.empty()) {
+        MergeRun &m = runs[heap[0]];
+        pend.insert(pend.end(), m.rec, m.rec + m.len);
+        if (pend.size() >= flush_at) {
+            if ((st = plo_bam_write(w, pend.data(), pend.size())) != PLO_OK) return done(st);
+            pend.clear();
+        }
+        if ((st = merge_next(m, n_ref)) != PLO_OK) return done(st);
+        if (!m.rec) {
+            heap[0] = heap.back();
+            heap.pop_back();
+        }
+        if (!heap.empty()) sift_down(0);
+    }
+    if (!pend.empty() && (st = plo_bam_write(w, pend.data(), pend.size())) != PLO_OK) return done(st);
+    return done(PLO_OK);
 }

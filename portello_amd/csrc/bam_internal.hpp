@@ -277,7 +277,9 @@ struct BgzfIn {
     // every refill: the first refill stays at CHUNK (the first window is out after one group's latency), the later ones take `later_chunk`
     // (PLO_BGZF_CHUNK_MB), so that the drain is paid once per gigabyte instead of once per two groups.
     size_t later_chunk = 0, n_fills = 0;
+    size_t chunk_cap = 0;  // != 0: every refill adds this much, the first included when set before it (plo_bam_merge_runs: many readers open at once, each with a small buffer)
     size_t chunk_now() {
+        if (chunk_cap) return chunk_cap;
         if (!later_chunk) {
             const char *e = getenv("PLO_BGZF_CHUNK_MB");
             const long mb = e ? atol(e) : 0;

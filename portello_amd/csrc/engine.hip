@@ -43,6 +43,7 @@
 #include "batch_core.hpp"
 #include "nm_core.hpp"
 #include "md_core.hpp"
+#include "sort_core.hpp"
 #include "window_core.hpp"
 #include "bgzf_walk.hpp"
 #include "index_pack.hpp"
@@ -1321,6 +1322,28 @@ __global__ __launch_bounds__(256) void k_nm(DevBatch bt, DevWork wk, DevNm d) { 
 __global__ __launch_bounds__(256) void k_md_count(DevBatch bt, DevWork wk, DevMd d) { md_items<false>(bt, wk, d); }
 __global__ __launch_bounds__(256) void k_md_emit(DevBatch bt, DevWork wk, DevMd d) { md_items<true>(bt, wk, d); }
 
+// ---- the window's records in coordinate order (sort_core.hpp) -------------------------------------------------------------
+// check + keys + the tile sort in LDS (12 KB), a merge launch per doubling of the runs, the lengths in sorted order, and (behind the
+// 64-bit scan) the permuted copy, a wave per 16 KB of output -- the only stage that touches the records' bytes
+__global__ __launch_bounds__(256) void k_sort_keys(DevSort d) {
+    __shared__ unsigned long long lk[SORT_TILE];
+    __shared__ uint32_t li[SORT_TILE];
+    sort_tile(d, blockIdx.x, lk, li);
+}
+__global__ __launch_bounds__(256) void k_sort_merge(const unsigned long long *sk, const uint32_t *si, unsigned long long *dk, uint32_t *di, uint32_t n, uint32_t run) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g < n) sort_merge_pair(sk, si, dk, di, n, run, g);
+}
+__global__ __launch_bounds__(256) void k_sort_gather(const uint32_t *perm, const unsigned long long *len, unsigned long long *slen, uint32_t n) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < n) slen[j] = len[perm[j]];
+}
+__global__ __launch_bounds__(256) void k_sort_copy(DevSort d, const uint32_t *perm, unsigned long long n_chunks) {
+    if (*d.err != SORT_NO_RECORD) return;  // a refused window: no byte is moved
+    const unsigned long long chunk = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id();
+    if (chunk < n_chunks) sort_copy_chunk(d, perm, chunk, wv::lane(), 64);  // (wave-uniform)
+}
+
 // ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
 // the label table: a thread per contig name
 __global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
@@ -1616,6 +1639,10 @@ struct plo_ctx {
     DevBuf md_len, md_off, md_partial, md_text, md_blk;
     HostBuf h_md;
     hipEvent_t mev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // plo_records_sort_dev: buffers of its own (the sorted copy of the window's bytes, two (key, index) arrays, lengths, offsets)
+    DevBuf so_key[2], so_idx[2], so_len, so_slen, so_off, so_partial, so_out, so_blk;
+    HostBuf h_so;
+    hipEvent_t sev[2] = {nullptr, nullptr};
     bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1974,6 +2001,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
                       &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk,
+                      &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -1983,7 +2011,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_so};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2003,6 +2031,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->nev[i]) (void)hipEventDestroy(c->nev[i]);
     for (int i = 0; i < 4; ++i)
         if (c->mev[i]) (void)hipEventDestroy(c->mev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -3508,6 +3538,109 @@ plo_status plo_md_dev(plo_ctx *c, const plo_batch_in *in, plo_md_out *out) {
     out->md_text = d.md_text;
     out->md_bytes = total;
     c->have_md = true;
+    return PLO_OK;
+}
+
+// The records at in->bytes in coordinate order (sort_core.hpp): k_sort_keys (check, keys, tiles sorted in LDS), a k_sort_merge per doubling
+// of the runs, k_sort_gather, the 64-bit scan of the lengths, k_sort_copy.  6 + ceil(log2(ceil(n / 1024))) launches, one wait behind the
+// copy: the copy looks at the check's word itself, so a refused window moves no byte.
+plo_status plo_records_sort_dev(plo_ctx *c, const plo_sort_in *in, plo_sort_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_record = UINT32_MAX;
+    c->err.clear();
+    const uint32_t n = in->n_records;
+    if (n && (!in->bytes || !in->record_off)) {
+        c->err = "plo_sort_in: the records and their offsets are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (n > 0x7ffffffeu || in->n_ref > 0x7fffffffu) {
+        c->err = "plo_records_sort_dev: more than 2^31 - 2 records or 2^31 - 1 references";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->sev[i]) HIP_TRY(c, hipEventCreate(&c->sev[i]));
+    HIP_TRY(c, c->so_off.ensure(((size_t)n + 1) * 8));
+    HIP_TRY(c, c->so_out.ensure((size_t)(n ? in->n_bytes : 0) + 16));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(c, c->so_key[i].ensure((size_t)std::max(1u, n) * 8));
+        HIP_TRY(c, c->so_idx[i].ensure((size_t)std::max(1u, n) * 4));
+    }
+    out->bytes = c->so_out.as<uint8_t>();
+    out->record_off = c->so_off.as<uint64_t>();
+    out->perm = c->so_idx[0].as<uint32_t>();
+    out->key = c->so_key[0].as<uint64_t>();
+    if (!n) {
+        HIP_TRY(c, hipMemsetAsync(c->so_off.p, 0, 8, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        return PLO_OK;
+    }
+    const uint32_t nb = (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK, n_tiles = (n + SORT_TILE - 1) / SORT_TILE, nt = (n + 255u) / 256u;
+    HIP_TRY(c, c->so_len.ensure((size_t)n * 8));
+    HIP_TRY(c, c->so_slen.ensure((size_t)n * 8));
+    HIP_TRY(c, c->so_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->so_blk.ensure(16));
+    HIP_TRY(c, c->h_so.ensure(32));
+    DevSort d;
+    memset(&d, 0, sizeof(d));
+    d.bytes = in->bytes;
+    d.n_bytes = in->n_bytes;
+    d.n = n;
+    d.record_off = in->record_off;
+    d.n_ref = in->n_ref;
+    for (int i = 0; i < 2; ++i) {
+        d.key[i] = c->so_key[i].as<unsigned long long>();
+        d.idx[i] = c->so_idx[i].as<uint32_t>();
+    }
+    d.len = c->so_len.as<unsigned long long>();
+    d.slen = c->so_slen.as<unsigned long long>();
+    unsigned long long *off = c->so_off.as<unsigned long long>();
+    d.new_off = off;
+    d.out = c->so_out.as<uint8_t>();
+    d.err = c->so_blk.as<int>();
+    d.n_mapped = c->so_blk.as<unsigned>() + 1;
+    uint32_t *h = c->h_so.as<uint32_t>();
+    h[0] = (uint32_t)SORT_NO_RECORD;
+    h[1] = 0;
+    h[4] = h[5] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->so_blk.p, h, 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->sev[0], st));
+    hipLaunchKernelGGL(k_sort_keys, dim3(n_tiles), dim3(SORT_THREADS), 0, st, d);
+    int cur = 0;
+    for (uint64_t run = SORT_TILE; run < n; run <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(k_sort_merge, dim3(nt), dim3(256), 0, st, (const unsigned long long *)d.key[cur], (const uint32_t *)d.idx[cur], d.key[cur ^ 1], d.idx[cur ^ 1], n, (uint32_t)run);
+    const uint32_t *perm = d.idx[cur];
+    hipLaunchKernelGGL(k_sort_gather, dim3(nt), dim3(256), 0, st, perm, (const unsigned long long *)d.len, d.slen, n);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.slen, n, nb, c->so_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->so_partial.as<unsigned long long>(), n, nb, off);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.slen, n, nb, (const unsigned long long *)c->so_partial.as<unsigned long long>(), off);
+    const unsigned long long n_chunks = (in->n_bytes + SORT_COPY_CHUNK - 1) / SORT_COPY_CHUNK;
+    if (n_chunks) hipLaunchKernelGGL(k_sort_copy, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, st, d, perm, n_chunks);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->sev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->so_blk.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)SORT_NO_RECORD) {
+        const uint32_t e = h[0];
+        HIP_TRY(c, hipMemcpy(h + 4, d.len + e, 8, hipMemcpyDeviceToHost));
+        static const char *const what[] = {"", "record_off: it must start at 0, not decrease and end at n_bytes", "its length: fewer than the 36 bytes of block_size and the fixed fields",
+                                           "block_size: block_size + 4 differs from the record's length", "refID: outside [-1, n_ref)", "pos: outside [-1, 2^31 - 2]"};
+        out->err_record = e;
+        out->bytes = nullptr;
+        out->record_off = nullptr;
+        out->perm = nullptr;
+        out->key = nullptr;
+        c->err = "plo_records_sort_dev: record " + std::to_string(e) + " is refused for " + (h[4] >= 1 && h[4] <= 5 ? what[h[4]] : "an unknown reason") + "; nothing was sorted";
+        return PLO_ERR_INVALID_ARG;
+    }
+    (void)hipEventElapsedTime(&out->sort_ms, c->sev[0], c->sev[1]);
+    out->n_bytes = in->n_bytes;
+    out->n_records = n;
+    out->perm = perm;
+    out->key = (const uint64_t *)d.key[cur];
+    out->n_mapped = h[1];
     return PLO_OK;
 }
 

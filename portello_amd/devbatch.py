@@ -428,7 +428,10 @@ class PinnedPool:
 class DeviceRecords:
     """host copy of a plo_records_out: what the writer takes (`bytes`, `n_bytes`) and the counts, as bam.PloRecordBuf has them"""
 
-    def __init__(self, ro: abi.PloRecordsOut, pool: Optional[PinnedPool] = None, dev=None, with_offsets: bool = False):
+    def __init__(self, ro: abi.PloRecordsOut, pool: Optional[PinnedPool] = None, dev=None, with_offsets: bool = False,
+                 sorted_out: Optional[abi.PloSortOut] = None):
+        """sorted_out: the plo_sort_out of api.Engine.records_sort_dev on `ro` -- its buffer (the same records in coordinate order) and
+        offsets are taken instead of ro's"""
         from .gather import device_view
 
         self.n_bytes, self.n_records = int(ro.n_bytes), int(ro.n_records)
@@ -442,11 +445,12 @@ class DeviceRecords:
         self._block = pool.take(nb) if pool is not None else torch.empty(nb, dtype=torch.uint8, pin_memory=True)
         t1 = time.perf_counter()
         self.record_off = None
+        src = sorted_out if sorted_out is not None else ro
         if self.n_bytes:
-            self._block[:self.n_bytes].copy_(device_view(ro.bytes, self.n_bytes, torch.uint8, dev), non_blocking=True)  # ONE copy, on the current stream
+            self._block[:self.n_bytes].copy_(device_view(src.bytes, self.n_bytes, torch.uint8, dev), non_blocking=True)  # ONE copy, on the current stream
         if with_offsets:
             off = torch.empty((self.n_records + 1) * 8, dtype=torch.uint8, pin_memory=True)
-            off.copy_(device_view(ro.record_off, (self.n_records + 1) * 8, torch.uint8, dev), non_blocking=True)
+            off.copy_(device_view(src.record_off, (self.n_records + 1) * 8, torch.uint8, dev), non_blocking=True)
             self.record_off = off.numpy().view(np.uint64)
         torch.cuda.current_stream().synchronize()
         self.block_s, self.copy_s = t1 - t0, time.perf_counter() - t1  # the page-locked block (a fresh one is an allocation) / the copy
@@ -467,13 +471,14 @@ class DeviceBlocks:
     bytes the blocks hold.  The record bytes themselves never leave the device."""
     is_blocks = True
 
-    def __init__(self, eng, ro: abi.PloRecordsOut, level: int, pool: Optional[PinnedPool] = None, dev=None):
+    def __init__(self, eng, ro: abi.PloRecordsOut, level: int, pool: Optional[PinnedPool] = None, dev=None, sorted_out: Optional[abi.PloSortOut] = None):
+        """sorted_out: as for DeviceRecords -- the sorted buffer is compressed instead of ro's"""
         from .gather import device_view
         import time
 
         self.n_records, self.n_lifted, self.n_unmapped_copies = int(ro.n_records), int(ro.n_lifted), int(ro.n_unmapped_copies)
         self.records_ms = float(ro.records_ms)
-        bo = eng.bgzf_compress_dev(ro.bytes, int(ro.n_bytes), level)
+        bo = eng.bgzf_compress_dev((sorted_out if sorted_out is not None else ro).bytes, int(ro.n_bytes), level)
         self.n_in, self.n_bytes, self.n_blocks, self.bgzf_ms = int(bo.n_in), int(bo.n_bytes), int(bo.n_blocks), float(bo.bgzf_ms)
         self._pool = pool
         nb = max(16, self.n_bytes)

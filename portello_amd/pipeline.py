@@ -72,10 +72,11 @@ class PipelineStats:
     part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
     nm_device_ms: float = 0.0  # emit_nm: HIP-event time of plo_nm_dev (NM:i of the lifted records)
     md_device_ms: float = 0.0  # emit_md: HIP-event time of plo_md_dev (MD:Z of the lifted records: count, scan, emit)
+    sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
     lift_detail_s: dict = field(default_factory=dict)  # device_finish: the lift stage by step (host clock; the steps that wait for the device carry its time)
-    out_paths: List[str] = field(default_factory=list)  # the output file, or the shards (out_shards > 1)
+    out_paths: List[str] = field(default_factory=list)  # the output file, the shards (out_shards > 1) or the runs in name order (sorted_runs)
     errors: List[str] = field(default_factory=list)
 
 
@@ -86,8 +87,16 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
-                   device_input: bool = False, emit_nm: bool = False, emit_md: bool = False) -> PipelineStats:  # noqa: E501
-    """emit_md (default off; needs device_records=True): every lifted record leaves with MD:Z, calmd's text against the reference
+                   device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False) -> PipelineStats:  # noqa: E501
+    """sorted_runs (default off; needs device_records=True, out_shards must be 1): every window's records are put in coordinate order on
+    the device (plo_records_sort_dev behind plo_records_build_dev: reference in header order, position, forward before reverse, unmapped
+    copies last, ties in input order) and leave as a run file of their own, a complete BAM with an SO:coordinate header, named
+    <stem>.r<reader:02d>w<window:06d><ext> after the window's sequence number at its reader -- `out_path` itself is not written.
+    PipelineStats.out_paths lists the runs in name order, which is the tie order of bam.merge_runs(st.out_paths, final_path) (or samtools
+    merge); the pipeline neither merges nor deletes.  A run of the pipeline without an output record writes one header-only run.  Works
+    with emit_nm, emit_md, device_batch, device_input, device_bgzf and part / n_parts; the unassembled file is untouched.  Off, every byte
+    and every file name is what it was.
+    emit_md (default off; needs device_records=True): every lifted record leaves with MD:Z, calmd's text against the reference
     chromosomes of the index (plo_md_dev between the finishing and plo_records_build_dev, which then writes the field behind ZM:C, behind
     NM:i with emit_nm, and cuts the MD the source record carried); the unmapped copies get none and keep theirs.  Combines with emit_nm:
     both on, the output needs no samtools calmd pass.  Off, every byte is what it was.
@@ -140,6 +149,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if sorted_runs and not device_records:
+        raise ValueError("sorted_runs sorts the records plo_records_build_dev leaves on the device: it needs device_records=True")
+    if sorted_runs and int(out_shards) > 1:
+        raise ValueError("sorted_runs writes a run file per window: out_shards > 1 has no meaning with it")
     if emit_nm and not device_records:
         raise ValueError("emit_nm counts NM on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
     if emit_md and not device_records:
@@ -180,8 +193,12 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         stem, ext = os.path.splitext(out_path)
         out_paths = [f"{stem}.{k}{ext}" for k in range(out_shards)]
     st.out_paths = list(out_paths)
-    hdr_out = bam.output_header(ref_names, ref_lens, cmdline=cmdline)
-    wrs = [bam.BamWriter(p_, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads // out_shards)) for p_ in out_paths]
+    hdr_out = bam.output_header(ref_names, ref_lens, cmdline=cmdline, sort_order="coordinate" if sorted_runs else "unsorted")
+    if sorted_runs:  # a writer per run, opened when the window's records arrive
+        run_stem, run_ext = os.path.splitext(out_path)
+        out_paths, wrs = [], []
+    else:
+        wrs = [bam.BamWriter(p_, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads // out_shards)) for p_ in out_paths]
     un = None
     if unassembled_path:
         un = bam.BamWriter(unassembled_path, bam.output_header(ref_names, ref_lens, cmdline=cmdline), ref_names, ref_lens, level=level,
@@ -228,7 +245,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                     break
                 with lock:
                     st.read_s += time.perf_counter() - t
-                put(q_win, win)
+                put(q_win, (win, (ci, n_win - 1)))  # (reader, the window's sequence number at it): names the window's run with sorted_runs
         except BaseException as e:  # noqa: BLE001
             st.errors.append(f"reader {ci}: {e!r}")
             abort.set()
@@ -240,9 +257,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         q_win = q_wins[ci]
         try:
             while True:
-                win = get(q_win)
-                if win is None:
+                item = get(q_win)
+                if item is None:
                     break
+                win, run_id = item
                 t = time.perf_counter()
                 if not win.n_records:
                     desc = None
@@ -258,7 +276,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                     desc = win.batch_desc(sparse_margin=sparse_margin, index_desc=ixd if sparse_margin is not None else None)
                 with lock:
                     st.batch_s += time.perf_counter() - t
-                put(q_in, (win, desc))
+                put(q_in, (win, desc, run_id))
         except BaseException as e:  # noqa: BLE001
             st.errors.append(f"batcher {ci}: {e!r}")
             abort.set()
@@ -297,7 +315,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 item = get(q_in)
                 if item is None:
                     break
-                win, desc = item
+                win, desc, run_id = item
                 rb = None
                 if desc is not None:
                     t = time.perf_counter()
@@ -333,11 +351,16 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 marks.append(("md", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
+                            srt, sort_ms = None, 0.0
+                            if sorted_runs and ro.n_records:
+                                srt = eng.records_sort_dev(ro.bytes, ro.n_bytes, ro.n_records, ro.record_off, len(ref_names))
+                                sort_ms = float(srt.sort_ms)
+                                marks.append(("sort", time.perf_counter()))
                             if device_bgzf:
-                                rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev)
+                                rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev, sorted_out=srt)
                                 marks.append(("bgzf", time.perf_counter() - rb.block_s - rb.copy_s))
                             else:
-                                rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev)
+                                rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev, sorted_out=srt)
                             now = time.perf_counter()
                             marks.append(("download: page-locked block", now - rb.copy_s))
                             marks.append(("download: copy", now))
@@ -349,6 +372,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.records_device_ms += rb.records_ms
                             st.nm_device_ms += nm_ms
                             st.md_device_ms += md_ms
+                            st.sort_device_ms += sort_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up
@@ -394,7 +418,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                         st.lifted += int(rb.n_lifted)
                         st.unmapped_copies += int(rb.n_unmapped_copies)
                         st.bytes_out += int(getattr(rb, "n_in", rb.n_bytes))
-                put(q_out, (win, rb))
+                put(q_out, (win, rb, run_id))
         except BaseException as e:  # noqa: BLE001
             st.errors.append(f"lift worker {k}: {e!r}")
             abort.set()
@@ -424,13 +448,21 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 item = get(q_out)
                 if item is None:
                     break
-                win, rb = item
+                win, rb, run_id = item
                 t = time.perf_counter()
                 if rb is not None and rb.n_bytes:
-                    if getattr(rb, "is_blocks", False):
-                        wrs[k].write_blocks((rb.bytes, rb.n_bytes))
+                    if sorted_runs:  # the window's run: a complete BAM of its own
+                        run_path = "%s.r%02dw%06d%s" % (run_stem, run_id[0], run_id[1], run_ext)
+                        wr = bam.BamWriter(run_path, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads))
+                        out_paths.append(run_path)
                     else:
-                        wrs[k].write((rb.bytes, rb.n_bytes))
+                        wr = wrs[k]
+                    if getattr(rb, "is_blocks", False):
+                        wr.write_blocks((rb.bytes, rb.n_bytes))
+                    else:
+                        wr.write((rb.bytes, rb.n_bytes))
+                    if sorted_runs:
+                        wr.close()
                 ub, nu = win.unmapped_bytes()
                 if nu:
                     with un_lock:
@@ -461,6 +493,12 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         t.join()
     for wr in wrs:
         wr.close()
+    if sorted_runs:
+        if not out_paths and not st.errors:  # no output record at all: one header-only run, so that a merge has a header
+            out_paths.append("%s.r%02dw%06d%s" % (run_stem, 0, 0, run_ext))
+            bam.BamWriter(out_paths[0], hdr_out, ref_names, ref_lens, level=level, n_threads=1).close()
+        out_paths.sort()
+        st.out_paths = list(out_paths)
     st.out_file_bytes = sum(os.path.getsize(p_) for p_ in out_paths if os.path.exists(p_))
     st.stage_done_s["output closed"] = time.perf_counter() - t0
     if un is not None:

@@ -20,6 +20,9 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_md_dev on the window (--md-out; runs alone or behind --nm-out): md_ms (count pass, scan, emit pass) beside the same window's nm_ms,
     lift, finish and records_ms event times, the text's bytes and the two passes' algorithmic bytes, and one device-to-device
     hipMemcpyAsync of that many bytes taken in the same process
+  - plo_records_sort_dev on the window's records (--sort-out; this leg runs alone): sort_ms beside the window's records_ms, and one
+    device-to-device hipMemcpyAsync of n_bytes taken in the same process (the floor of the permuted copy).  perm, key, record_off and the
+    bytes are compared with the order computed on the host (numpy, from the definition of the key) before anything is timed
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -33,6 +36,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --part-out profiles/r11_part_start.json
     python tools/bench_records.py --reads 50000 --nm-out profiles/r12_nm_window.json
     python tools/bench_records.py --reads 50000 --nm-out profiles/r13_nm_window.json --md-out profiles/r13_md_window.json
+    python tools/bench_records.py --reads 50000 --sort-out profiles/r14_sort_window.json
 """
 import argparse
 import ctypes as C
@@ -517,6 +521,84 @@ def md_leg(a, win, index, cn, rn, dev):
     return res, bool(same)
 
 
+def sort_leg(a, win, index, cn, rn, dev):
+    """ONE window: plo_records_sort_dev on the records of plo_records_build_dev, against the host's expected order and a device-to-device
+    copy of the same bytes"""
+    import numpy as np
+    import torch
+
+    from portello_amd import api, build, devbatch
+    from portello_amd.gather import device_view
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    out = eng.liftover_batch_dev(ddesc)
+    eng.compact_output_dev(out)
+    eng.finish_batch_dev(ddesc, up.finish_in())
+    eng.sa_segments_dev(sa_in)
+    ro = eng.records_build_dev(ddesc, rin)
+    n, nb, n_ref = int(ro.n_records), int(ro.n_bytes), len(rn)
+
+    def down(ptr, count, dtype):
+        return device_view(ptr, count * np.dtype(dtype).itemsize, torch.uint8, dev).cpu().numpy().view(dtype) if count else np.zeros(0, dtype)
+
+    # the expected order, from the definition of the key
+    data, off = down(ro.bytes, nb, np.uint8), down(ro.record_off, n + 1, np.uint64).astype(np.int64)
+    at = off[:-1]
+    fld = lambda o, w: sum(data[at + o + k].astype(np.int64) << (8 * k) for k in range(w))
+    ref, pos, flag = fld(4, 4).astype(np.uint32).view(np.int32).astype(np.int64), fld(8, 4).astype(np.uint32).view(np.int32).astype(np.int64), fld(18, 2)
+    key = (np.where(ref < 0, n_ref, ref) << 32) | ((pos + 1) << 1) | ((flag >> 4) & 1)
+    perm = np.lexsort((np.arange(n), key))
+    lens = np.diff(off)[perm]
+    exp_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    so = eng.records_sort_dev(ro.bytes, nb, n, ro.record_off, n_ref)
+    same = (int(so.n_records) == n and int(so.n_bytes) == nb and np.array_equal(down(so.perm, n, np.uint32), perm.astype(np.uint32)) and
+            np.array_equal(down(so.key, n, np.uint64), key[perm].astype(np.uint64)) and np.array_equal(down(so.record_off, n + 1, np.uint64), exp_off) and
+            int(so.n_mapped) == int((ref >= 0).sum()))
+    if same and n:
+        got = down(so.bytes, nb, np.uint8)
+        same = all(np.array_equal(got[int(exp_off[j]):int(exp_off[j + 1])], data[int(off[i]):int(off[i + 1])]) for j, i in enumerate(perm))
+        del got
+    same = same and np.array_equal(down(ro.bytes, nb, np.uint8), data)  # the input is unchanged
+    sort_ms, wall_ms, rec_ms = [], [], []
+    for k in range(a.warmup + a.reps):
+        ro = eng.records_build_dev(ddesc, rin)
+        t0 = time.perf_counter()
+        so = eng.records_sort_dev(ro.bytes, nb, n, ro.record_off, n_ref)
+        t1 = time.perf_counter()
+        if k >= a.warmup:
+            sort_ms.append(float(so.sort_ms))
+            wall_ms.append((t1 - t0) * 1e3)
+            rec_ms.append(float(ro.records_ms))
+    src, dst = torch.empty(max(16, nb), dtype=torch.uint8, device=dev), torch.empty(max(16, nb), dtype=torch.uint8, device=dev)
+    src.zero_()
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    med = lambda v: sorted(v)[len(v) // 2]
+    tiles = (n + 1023) // 1024
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "records": n, "n_bytes": nb, "n_ref": n_ref, "n_mapped": int(so.n_mapped),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "equals_host_order": bool(same), "launches_per_call": 6 + max(0, (tiles - 1).bit_length()),
+           "sort_ms": stats(sort_ms), "sort_call_wall_ms": stats(wall_ms), "records_ms": stats(rec_ms), "d2d_copy_n_bytes_ms": stats(d2d),
+           "sort_gbs_read_plus_write": 2 * nb / med(sort_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * nb / med(d2d) / 1e6,
+           "sort_over_d2d_copy_time": med(sort_ms) / med(d2d), "sort_over_records_time": med(sort_ms) / med(rec_ms)}
+    return res, bool(same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -534,6 +616,7 @@ def main():
     ap.add_argument("--part-out", default="", help="run the part leg (plo_part_start_dev and the first cut of part 1 of 2 against plo_bam_open_range) alone and write its JSON there")
     ap.add_argument("--nm-out", default="", help="run the NM leg (plo_nm_dev beside the window's lift, finish and records times, against a device-to-device copy) alone and write its JSON there")
     ap.add_argument("--md-out", default="", help="run the MD leg (plo_md_dev beside the window's nm, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out")
+    ap.add_argument("--sort-out", default="", help="run the sort leg (plo_records_sort_dev on the window's records, against the host's expected order and a device-to-device copy of n_bytes) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -575,6 +658,15 @@ def main():
             with open(a.cut_out, "w") as fh:
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
+    if a.sort_out:
+        sres, ok = sort_leg(a, win, index, cn, rn, dev)
+        win.close()
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.sort_out)), exist_ok=True)
+        with open(a.sort_out, "w") as fh:
+            fh.write(json.dumps(sres, indent=1) + "\n")
+        print(json.dumps(sres))
         sys.exit(0 if ok else 1)
     if a.nm_out or a.md_out:
         ok = True
