@@ -190,6 +190,32 @@ plo_status plo_bam_write(plo_bam_writer *w, const uint8_t *record_bytes, uint64_
    and leaves the file untouched.  The run carries no EOF block: plo_bam_writer_close writes it. */
 plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blocks, uint64_t n_bytes);
 plo_status plo_bam_writer_close(plo_bam_writer *w);
+/* The BAM index of the file the writer is writing (API version 15; SAMv1 5.2), for coordinate-sorted output.  The writer never looks into
+ * a record: it takes plo_index_entry values (portello_liftover.h: plo_records_index_dev on the device, or any caller that follows its rule)
+ * and notes, for every BGZF block it emits -- plo_bam_write, the partial-block flush and plo_bam_write_blocks, which reads ISIZE of the
+ * blocks it walks anyway --, where the block starts in the record stream and in the file.
+ *   plo_bam_writer_index_enable   right behind plo_bam_writer_open, before any record byte; an @SQ longer than 2^29 -> PLO_ERR_INVALID_ARG
+ *   plo_bam_writer_index_add      BEFORE the plo_bam_write / plo_bam_write_blocks of the same records; entries[i].off counts from that
+ *                                 write's first byte, the writer adds the length of its record stream so far
+ *   plo_bam_writer_close          checks that entries and bytes tile each other (every add's first entry at the first byte written behind
+ *                                 it, every entry at least 36 bytes in front of the next, the last inside the bytes written, no bytes
+ *                                 without entries, (reference, beg) not decreasing), else PLO_ERR_INVALID_ARG and no index -- the BAM
+ *                                 is closed as without one --; then writes bai_path.  Offsets are all the writer has: an entry
+ *                                 left out of an add, the last or one in the middle, looks like one longer record in front of it
+ *                                 and yields a well-formed index that omits the record.  The count is the caller's to check:
+ *                                 n must be the number of records of the write (plo_index_out.n_records against the records
+ *                                 handed to the writer, as the Python pipeline does; the merge makes one entry per record it reads)
+ * voff(o) = (file offset of the block that holds stream byte o) << 16 | o's offset in it, and (file offset of the EOF block) << 16 for the
+ * stream's end; a record's chunk runs from voff(its start) to voff(the next record's start), so a record that starts at a block boundary
+ * belongs to the new block.  Layout: magic, n_ref; per reference the bins in ascending order, in a bin the chunks in file order; records
+ * that follow each other in the file with one (reference, bin) make one chunk, nothing else is merged, no bin is folded into its parent;
+ * pseudo-bin 37450 last for a reference with records: (voff of its first record, voff behind its last), (records with FLAG & 4 clear,
+ * set); linear index: every placed record sets the 16 kb windows beg >> 14 .. (end - 1) >> 14 to voff(its start) where unset, n_intv is
+ * the highest window + 1, an unset window takes the next set one's value; a reference without records has n_bin = n_intv = 0; n_no_coor
+ * (the refID -1 records) ends the file. */
+plo_status plo_bam_writer_index_enable(plo_bam_writer *w, const char *bai_path);
+plo_status plo_bam_writer_index_add(plo_bam_writer *w, const plo_index_entry *entries, uint64_t n);
+
 /* bytes the writer has put into its file so far (header blocks included, an open partial block not) */
 uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w);
 
@@ -204,6 +230,11 @@ uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w);
  * Every message names the run.  A merge that fails leaves no file at out_path (what it had written is removed).  Every run is read
  * through a buffer of 4 MB refills, from the header on, so some hundred runs can be open at once. */
 plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_paths, const char *out_path, int level, int n_threads);
+/* The same merge with the index of its output at bai_path (API version 15); plo_bam_merge_runs is this call with bai_path == NULL, and the
+ * merged BAM is byte for byte the same with and without.  The entries come from the one-thread form of plo_records_index_dev's rule
+ * (index_core.hpp); a record it refuses (a CIGAR that leaves the record, an end behind 2^29) -> PLO_ERR_DATA naming the run and the record.
+ * A merge that fails leaves neither file. */
+plo_status plo_bam_merge_runs_indexed(const char *const *paths, uint32_t n_paths, const char *out_path, const char *bai_path, int level, int n_threads);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Phase 1: the contig->reference index from the assembly->reference BAM (scan_contig_bam,

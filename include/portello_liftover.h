@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 14 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs */
+#define PLO_API_VERSION 15 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -504,6 +504,51 @@ typedef struct plo_sort_out {
 } plo_sort_out;
 
 plo_status plo_records_sort_dev(plo_ctx *ctx, const plo_sort_in *in, plo_sort_out *out);
+
+/* ---- Index entries of coordinate-sorted records (device-resident, opt-in; API version 15) -----------------------------
+ * What a BAM index (BAI, SAMv1 5.2) needs of every record at `bytes` -- typically plo_sort_out::bytes / record_off --, 24 bytes a record,
+ * so that the host can write <run>.bai without holding an uncompressed record (plo_bam_writer_index_add, portello_bam.h).
+ *   refID >= 0   beg = max(pos, 0); rlen = the summed lengths of the ops M, D, N, =, X (codes 0, 2, 3, 7, 8) of the in-record CIGAR (64-bit;
+ *                the placeholder <l_seq>S<ref_len>N of a record with more than 65 535 ops needs no special case, codes 9-15 consume
+ *                nothing); end = beg + rlen, or beg + 1 when FLAG & 4 is set or rlen == 0
+ *   refID == -1  beg = -1, end = 0, bin 4680
+ * Checked on the device before a byte of a record is trusted, kinds in err_kind:
+ *   1 .. 5  what plo_records_sort_dev checks, in its order: record_off, the 36 bytes, block_size, refID in [-1, n_ref), pos
+ *   6       36 + l_read_name + 4 n_cigar_op > 4 + block_size: the CIGAR leaves the record
+ *   7       end > 2^29: BAI cannot address it
+ *   8       the pair (refID < 0 ? n_ref : refID, pos) is lower than the previous record's: the buffer is not coordinate sorted (the strand
+ *           bit of plo_records_sort_dev's key is no part of the test)
+ * A record reports the first kind it breaks in this order.  Any -> PLO_ERR_INVALID_ARG, err_record the LOWEST such record, err_kind what it
+ * broke, no entries handed out, plo_last_error names both.  n_records == 0 -> PLO_OK; NULL bytes or record_off with n_records > 0 ->
+ * PLO_ERR_INVALID_ARG; more than 2^27 - 1 records -> PLO_ERR_RANGE.
+ * A wave takes a record: the ops are read a lane each, coalesced, and summed across the lanes.  One kernel, no LDS, ONE wait.  The input
+ * and every other result on the context stay untouched; `entry` (24 n_records bytes, grown to the largest call) is valid until the
+ * context's next plo_records_index_dev. */
+typedef struct plo_index_entry {
+    uint64_t off;                 /* record_off[i]: where the record's block_size stands in the buffer */
+    int32_t ref_id;               /* -1: unplaced */
+    int32_t beg, end;             /* 0-based half-open */
+    uint32_t flags;               /* bit 0: FLAG & 4 (unmapped); bits 16..31: reg2bin(beg, end) */
+} plo_index_entry;
+
+typedef struct plo_index_in {
+    const uint8_t *bytes;         /* device: coordinate-sorted records, each prefixed by its block_size (plo_sort_out::bytes) */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    const uint64_t *record_off;   /* device [n_records + 1] */
+    uint32_t n_ref;               /* @SQ count of the output header */
+} plo_index_in;
+
+typedef struct plo_index_out {
+    const plo_index_entry *entry; /* device [n_records], owned by the context until its next plo_records_index_dev */
+    uint32_t n_records;
+    uint32_t n_placed;            /* records with refID >= 0 */
+    uint32_t err_record;          /* PLO_ERR_INVALID_ARG from the device check: lowest offending record, else UINT32_MAX */
+    uint32_t err_kind;            /* what it broke (1 .. 8 above), else 0 */
+    float index_ms;               /* HIP-event time of the call's kernel */
+} plo_index_out;
+
+plo_status plo_records_index_dev(plo_ctx *ctx, const plo_index_in *in, plo_index_out *out);
 
 /* ---- The liftover batch (device-resident) ------------------------------------------------------------------------
  * Builds the plo_batch_in / plo_finish_in of a window from its records as they stand in device memory: what plo_bam_window_batch_raw

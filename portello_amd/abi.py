@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 14  # include/portello_liftover.h
+PLO_API_VERSION = 15  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -198,6 +198,23 @@ class PloSortIn(C.Structure):
 class PloSortOut(C.Structure):
     _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("perm", _u32p), ("key", _u64p),
                 ("n_mapped", C.c_uint32), ("err_record", C.c_uint32), ("sort_ms", C.c_float)]
+
+
+class PloIndexEntry(C.Structure):
+    """24 bytes: off, ref_id, beg, end, flags (bit 0: FLAG & 4; bits 16..31: reg2bin(beg, end))"""
+    _fields_ = [("off", C.c_uint64), ("ref_id", C.c_int32), ("beg", C.c_int32), ("end", C.c_int32), ("flags", C.c_uint32)]
+
+
+INDEX_ENTRY_DTYPE = np.dtype([("off", "<u8"), ("ref_id", "<i4"), ("beg", "<i4"), ("end", "<i4"), ("flags", "<u4")])  # plo_index_entry as a numpy record
+
+
+class PloIndexIn(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("n_ref", C.c_uint32)]
+
+
+class PloIndexOut(C.Structure):
+    _fields_ = [("entry", C.POINTER(PloIndexEntry)), ("n_records", C.c_uint32), ("n_placed", C.c_uint32), ("err_record", C.c_uint32), ("err_kind", C.c_uint32),
+                ("index_ms", C.c_float)]
 
 
 class PloBgzfOut(C.Structure):

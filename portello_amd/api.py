@@ -82,6 +82,8 @@ def load_library(path: Optional[str] = None):
     L.plo_md_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloMdOut)]
     L.plo_records_sort_dev.restype = C.c_int
     L.plo_records_sort_dev.argtypes = [vp, C.POINTER(abi.PloSortIn), C.POINTER(abi.PloSortOut)]
+    L.plo_records_index_dev.restype = C.c_int
+    L.plo_records_index_dev.argtypes = [vp, C.POINTER(abi.PloIndexIn), C.POINTER(abi.PloIndexOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_bgzf_inflate_dev.restype = C.c_int
@@ -292,6 +294,22 @@ class Engine:
             msg = self.lib.plo_last_error(self.handle)
             e = PortelloError(st, f"plo_records_sort_dev: {msg.decode() if msg else ''}")
             e.err_record = int(out.err_record)
+            raise e
+        return out
+
+    def records_index_dev(self, bytes_ptr, n_bytes: int, n_records: int, record_off_ptr, n_ref: int) -> abi.PloIndexOut:
+        """What a BAM index needs of every record of the coordinate-sorted buffer at the DEVICE address `bytes_ptr` (records_sort_dev's
+        bytes / record_off): plo_records_index_dev, a plo_index_entry of 24 bytes a record, on the device, valid until the engine's next
+        records_index_dev; the input stays unchanged.  A record the device check refuses (what records_sort_dev refuses, a CIGAR that
+        leaves its record, an end behind 2^29, a record in front of the one before it) raises PortelloError with status
+        PLO_ERR_INVALID_ARG, the lowest such record in `err_record` and what it broke in `err_kind`."""
+        iin = abi.PloIndexIn(C.cast(bytes_ptr, abi._u8p), int(n_bytes), int(n_records), C.cast(record_off_ptr, abi._u64p), int(n_ref))
+        out = abi.PloIndexOut()
+        st = self.lib.plo_records_index_dev(self.handle, C.byref(iin), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_records_index_dev: {msg.decode() if msg else ''}")
+            e.err_record, e.err_kind = int(out.err_record), int(out.err_kind)
             raise e
         return out
 

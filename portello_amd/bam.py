@@ -4,6 +4,7 @@ line-by-line correspondence)."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -81,6 +82,12 @@ def lib():
         L.plo_bam_output_header_so.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
         L.plo_bam_merge_runs.restype = C.c_int
         L.plo_bam_merge_runs.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_int, C.c_int]
+        L.plo_bam_merge_runs_indexed.restype = C.c_int
+        L.plo_bam_merge_runs_indexed.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
+        L.plo_bam_writer_index_enable.restype = C.c_int
+        L.plo_bam_writer_index_enable.argtypes = [vp, C.c_char_p]
+        L.plo_bam_writer_index_add.restype = C.c_int
+        L.plo_bam_writer_index_add.argtypes = [vp, vp, C.c_uint64]
         L.plo_bam_free_text.restype = None
         L.plo_bam_free_text.argtypes = [vp]
         L.plo_bam_writer_open.restype = C.c_int
@@ -300,22 +307,51 @@ def output_header(ref_names: Sequence[str], ref_lens: Sequence[int], program_nam
     return s
 
 
-def merge_runs(paths: Sequence[str], out_path: str, level: int = 0, n_threads: int = 4) -> None:
-    """plo_bam_merge_runs: the coordinate-sorted BAM files `paths` (the runs of run_bam_to_bam(sorted_runs=True), in
+def merge_runs(paths: Sequence[str], out_path: str, level: int = 0, n_threads: int = 4, index: bool = False) -> None:
+    """index=True: plo_bam_merge_runs_indexed -- the same merged file, byte for byte, and its BAM index at out_path + ".bai"; a record
+    that cannot be indexed (a CIGAR that leaves it, an end behind 2^29) is PLO_ERR_DATA, and a failed merge leaves neither file.
+    plo_bam_merge_runs: the coordinate-sorted BAM files `paths` (the runs of run_bam_to_bam(sorted_runs=True), in
     PipelineStats.out_paths order) merged into one, ordered by (key, index of the path, order inside the path).  Raises PortelloError:
     PLO_ERR_INVALID_ARG (no path, differing headers), PLO_ERR_DATA (a run out of order), PLO_ERR_IO (a truncated or corrupt run)."""
     arr = _names(list(paths))
-    _check(lib().plo_bam_merge_runs(arr, len(paths), out_path.encode(), int(level), int(n_threads)), "plo_bam_merge_runs")
+    if index:
+        _check(lib().plo_bam_merge_runs_indexed(arr, len(paths), out_path.encode(), (out_path + ".bai").encode(), int(level), int(n_threads)), "plo_bam_merge_runs_indexed")
+    else:
+        _check(lib().plo_bam_merge_runs(arr, len(paths), out_path.encode(), int(level), int(n_threads)), "plo_bam_merge_runs")
 
 
 class BamWriter:
-    def __init__(self, path: str, header_text: str, ref_names: Sequence[str], ref_lens: Sequence[int], level: int = 0, n_threads: int = 4):
+    def __init__(self, path: str, header_text: str, ref_names: Sequence[str], ref_lens: Sequence[int], level: int = 0, n_threads: int = 4,
+                 index_path: Optional[str] = None):
+        """index_path: the file's BAM index is written there when the writer closes (plo_bam_writer_index_enable); every write /
+        write_blocks then follows an index_add of its records' entries"""
         h = C.c_void_p()
         rn = _names(ref_names)
         rl = (C.c_uint32 * max(1, len(ref_lens)))(*[int(x) for x in ref_lens])
         _check(lib().plo_bam_writer_open(path.encode(), header_text.encode(), len(ref_names), rn, rl, level, n_threads, C.byref(h)),
                f"plo_bam_writer_open({path})")
         self.handle = h
+        if index_path is not None:
+            st = lib().plo_bam_writer_index_enable(h, index_path.encode())
+            if st != 0:  # no writer for the caller: the message first (close may set its own), then no header-only file is left behind
+                msg = lib().plo_bam_last_error().decode(errors="replace")
+                try:
+                    self.close()
+                except api.PortelloError:
+                    pass
+                if os.path.exists(path):
+                    os.remove(path)
+                raise api.PortelloError(st, f"plo_bam_writer_index_enable({index_path}): {msg}")
+
+    def index_add(self, entries):
+        """the plo_index_entry values (a numpy array of abi.INDEX_ENTRY_DTYPE, or (pointer, count)) of the records of the NEXT write /
+        write_blocks, offsets counted from that write's first byte (plo_bam_writer_index_add)"""
+        if isinstance(entries, np.ndarray):
+            a = np.ascontiguousarray(entries)
+            assert a.dtype.itemsize == 24
+            _check(lib().plo_bam_writer_index_add(self.handle, a.ctypes.data_as(C.c_void_p), len(a)), "plo_bam_writer_index_add")
+        else:
+            _check(lib().plo_bam_writer_index_add(self.handle, C.cast(entries[0], C.c_void_p), int(entries[1])), "plo_bam_writer_index_add")
 
     def write(self, data):
         if isinstance(data, (bytes, bytearray)):

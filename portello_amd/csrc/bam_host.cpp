@@ -4,9 +4,11 @@
 // published behaviour (third party, absent from the reference tree).
 #include <errno.h>
 #include <chrono>
+#include <memory>
 #include <sys/uio.h>
 
 #include "bam_internal.hpp"
+#include "index_core.hpp"
 
 namespace {
 thread_local std::string g_bam_err;
@@ -1162,8 +1164,23 @@ extern "C" char *plo_bam_output_header_so(uint32_t n_ref, const char *const *ref
 }
 extern "C" void plo_bam_free_text(char *text) { free(text); }
 
+// what plo_bam_writer_index_enable switches on: where every BGZF block of the record stream starts, in the stream and in the file, and the
+// entries of the records, their offsets made absolute
+struct BaiState {
+    std::string path;
+    std::vector<uint64_t> blk_stream, blk_file;
+    uint64_t emitted = 0;     // record-stream bytes that have gone out in blocks
+    uint64_t stream_len = 0;  // record-stream bytes taken so far (the open partial block included)
+    std::vector<plo_index_entry> ent;
+    std::vector<std::pair<size_t, uint64_t>> adds;  // per plo_bam_writer_index_add: (its first entry, the stream length when it came)
+};
+
 struct plo_bam_writer {
     int fd = -1;
+    uint32_t n_ref = 0;
+    std::vector<uint32_t> ref_lens;
+    uint64_t hdr_end = 0;  // file_off behind the header's blocks
+    std::unique_ptr<BaiState> bai;
     int level = 0, threads = 1;
     bool seekable = false;
     uint64_t file_off = 0;
@@ -1260,6 +1277,13 @@ plo_status plo_bam_writer::emit(const uint8_t *src, size_t n) {
             }
         });
         if (wbad) return fail(PLO_ERR_IO, "write failed");
+        if (bai) {
+            for (size_t b = 0; b < nblk; ++b) {
+                bai->blk_stream.push_back(bai->emitted + (uint64_t)b * BLOCK);
+                bai->blk_file.push_back(file_off + (uint64_t)b * (18 + 5 + BLOCK + 8));
+            }
+            bai->emitted += n;
+        }
         file_off += (uint64_t)(nblk - 1) * (18 + 5 + BLOCK + 8) + (18 + 5 + std::min(BLOCK, n - (nblk - 1) * BLOCK) + 8);
         return PLO_OK;
     }
@@ -1363,6 +1387,13 @@ plo_status plo_bam_writer::emit(const uint8_t *src, size_t n) {
             }
         }
     }
+    if (bai) {
+        for (size_t b = 0; b < nblk; ++b) {
+            bai->blk_stream.push_back(bai->emitted + (uint64_t)b * BLOCK);
+            bai->blk_file.push_back(file_off + at[b]);
+        }
+        bai->emitted += n;
+    }
     file_off += at[nblk];
     if (dbg)
         fprintf(stderr, "[plo] bgzf write: %.1f MB in %zu blocks: build %.3f s, write %.3f s\n", n / 1e6, nblk, std::chrono::duration<double>(t1 - t0).count(),
@@ -1371,6 +1402,7 @@ plo_status plo_bam_writer::emit(const uint8_t *src, size_t n) {
 }
 
 plo_status plo_bam_writer::put(const uint8_t *src, size_t n) {
+    if (bai) bai->stream_len += n;
     if (!pend.empty()) {  // complete the open block first
         size_t take = std::min(n, BLOCK - pend.size());
         pend.insert(pend.end(), src, src + take);
@@ -1426,7 +1458,33 @@ extern "C" plo_status plo_bam_writer_open(const char *path, const char *header_t
         delete w;
         return st;
     }
+    w->n_ref = n_ref;
+    w->ref_lens.assign(ref_lens, ref_lens + n_ref);
+    w->hdr_end = w->file_off;
     *out = w;
+    return PLO_OK;
+}
+
+extern "C" plo_status plo_bam_writer_index_enable(plo_bam_writer *w, const char *bai_path) {
+    if (!w || !bai_path) return PLO_ERR_INVALID_ARG;
+    if (w->bai) return fail(PLO_ERR_INVALID_ARG, "plo_bam_writer_index_enable: the index is enabled already");
+    if (w->file_off != w->hdr_end || !w->pend.empty())
+        return fail(PLO_ERR_INVALID_ARG, "plo_bam_writer_index_enable: record bytes have been written; the call comes right behind plo_bam_writer_open");
+    for (uint32_t i = 0; i < w->n_ref; ++i)
+        if ((long long)w->ref_lens[i] > plo::INDEX_MAX_END)
+            return fail(PLO_ERR_INVALID_ARG, "plo_bam_writer_index_enable: @SQ " + std::to_string(i) + " is longer than 2^29, which a BAM index cannot address");
+    w->bai.reset(new BaiState());
+    w->bai->path = bai_path;
+    return PLO_OK;
+}
+
+extern "C" plo_status plo_bam_writer_index_add(plo_bam_writer *w, const plo_index_entry *entries, uint64_t n) {
+    if (!w || (n && !entries)) return PLO_ERR_INVALID_ARG;
+    if (!w->bai) return fail(PLO_ERR_INVALID_ARG, "plo_bam_writer_index_add: the writer has no index (plo_bam_writer_index_enable)");
+    BaiState &b = *w->bai;
+    b.adds.push_back({b.ent.size(), b.stream_len});
+    b.ent.insert(b.ent.end(), entries, entries + n);
+    for (size_t k = b.ent.size() - (size_t)n; k < b.ent.size(); ++k) b.ent[k].off += b.stream_len;
     return PLO_OK;
 }
 
@@ -1441,6 +1499,7 @@ extern "C" plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blo
     std::vector<uint64_t> cut;  // starts of the pieces the writers take (a few MB each, at block boundaries)
     const uint64_t piece = (uint64_t)4 << 20;
     uint64_t at = 0;
+    std::vector<std::pair<uint64_t, uint32_t>> isize;  // with an index: (where a block starts, the bytes it inflates to)
     while (at < n) {
         static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
         if (n - at < 18 + 2 + 8 || memcmp(blocks + at, hdr, 4) != 0 || memcmp(blocks + at + 10, hdr + 10, 6) != 0)
@@ -1448,6 +1507,7 @@ extern "C" plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blo
         const uint64_t bs = (uint64_t)(blocks[at + 16] | (blocks[at + 17] << 8)) + 1;
         if (bs < 18 + 2 + 8 || bs > n - at) return fail(PLO_ERR_INVALID_ARG, "plo_bam_write_blocks: the block at offset " + std::to_string(at) + " runs past the end");
         if (cut.empty() || at - cut.back() >= piece) cut.push_back(at);
+        if (w->bai) isize.push_back({at, rd32(blocks + at + bs - 4)});
         at += bs;
     }
     if (!n) return PLO_OK;
@@ -1488,9 +1548,120 @@ extern "C" plo_status plo_bam_write_blocks(plo_bam_writer *w, const uint8_t *blo
             left -= (size_t)k;
         }
     }
+    if (w->bai) {
+        BaiState &b = *w->bai;
+        for (const auto &bl : isize) {
+            b.blk_stream.push_back(b.emitted);
+            b.blk_file.push_back(w->file_off + bl.first);
+            b.emitted += bl.second;
+        }
+        b.stream_len = b.emitted;
+    }
     w->file_off += n;
     return PLO_OK;
 }
+
+namespace {
+void put_u32(std::vector<uint8_t> &o, uint32_t v) {
+    uint8_t b[4];
+    wr32(b, v);
+    o.insert(o.end(), b, b + 4);
+}
+void put_u64(std::vector<uint8_t> &o, uint64_t v) {
+    put_u32(o, (uint32_t)v);
+    put_u32(o, (uint32_t)(v >> 32));
+}
+// The index of a closed record stream (SAMv1 5.2), layout fully determined: per reference the bins in ascending order, in a bin the chunks
+// in file order, a chunk grown only by the records that follow each other in one bin; pseudo-bin 37450 last; the linear index filled
+// backwards.  eof_off: where the EOF block stands.  -> "" or why the entries and the bytes do not tile each other
+std::string bai_build(const BaiState &b, uint32_t n_ref, uint64_t eof_off, std::vector<uint8_t> &out) {
+    const size_t n = b.ent.size();
+    if (b.emitted != b.stream_len) return "bytes are left outside a block";
+    for (size_t a = 0; a < b.adds.size(); ++a) {  // every add covers the bytes from its stream length to the next add's (the last: to the end)
+        const size_t e0 = b.adds[a].first, e1 = a + 1 < b.adds.size() ? b.adds[a + 1].first : n;
+        const uint64_t s0 = b.adds[a].second, s1 = a + 1 < b.adds.size() ? b.adds[a + 1].second : b.stream_len;
+        if (e0 == e1) {
+            if (s0 != s1) return "bytes were written behind an index_add without entries";
+            continue;
+        }
+        if (b.ent[e0].off != s0) return "the first entry of an index_add does not start at the first byte written behind it";
+        for (size_t k = e0; k < e1; ++k) {
+            const uint64_t next = k + 1 < e1 ? b.ent[k + 1].off : s1;
+            if (next < b.ent[k].off || next - b.ent[k].off < 36) return "entry " + std::to_string(k) + " does not end where the next record (or the written bytes) begins";
+        }
+    }
+    if (b.adds.empty() ? b.stream_len != 0 : b.adds[0].second != 0) return "bytes were written without entries";
+    for (size_t k = 0; k < n; ++k) {
+        const plo_index_entry &e = b.ent[k];
+        if (e.ref_id < -1 || (e.ref_id >= 0 && (uint32_t)e.ref_id >= n_ref) || (e.ref_id >= 0 && (e.beg < 0 || e.end <= e.beg || (long long)e.end > plo::INDEX_MAX_END)))
+            return "entry " + std::to_string(k) + " lies outside the header's references or what a BAM index can address";
+        if (k && plo::index_order_breaks(e.ref_id, e.beg, b.ent[k - 1].ref_id, b.ent[k - 1].beg, n_ref)) return "entry " + std::to_string(k) + " lies in front of the entry before it";
+    }
+    auto voff = [&](uint64_t o) -> uint64_t {
+        if (o >= b.stream_len) return eof_off << 16;
+        const size_t k = (size_t)(std::upper_bound(b.blk_stream.begin(), b.blk_stream.end(), o) - b.blk_stream.begin()) - 1;  // the last block that starts at or before o
+        return (b.blk_file[k] << 16) | (o - b.blk_stream[k]);
+    };
+    out.clear();
+    out.insert(out.end(), {'B', 'A', 'I', 1});
+    put_u32(out, n_ref);
+    size_t k = 0;
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        const size_t k0 = k;
+        while (k < n && b.ent[k].ref_id == (int32_t)r) ++k;
+        if (k == k0) {
+            put_u32(out, 0);
+            put_u32(out, 0);
+            continue;
+        }
+        std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> chunks;  // (bin, chunk) in file order; sorted by bin below, stably
+        std::vector<uint64_t> lin;
+        uint64_t n_map = 0, n_unm = 0;
+        for (size_t j = k0; j < k; ++j) {
+            const plo_index_entry &e = b.ent[j];
+            const uint32_t bin = plo::index_reg2bin(e.beg, e.end);
+            const uint64_t v0 = voff(e.off), v1 = voff(j + 1 < n ? b.ent[j + 1].off : b.stream_len);
+            if (j > k0 && chunks.back().first == bin) chunks.back().second.second = v1;
+            else chunks.push_back({bin, {v0, v1}});
+            (e.flags & 1u ? n_unm : n_map)++;
+            const size_t w0 = (size_t)(e.beg >> 14), w1 = (size_t)((e.end - 1) >> 14);
+            if (lin.size() <= w1) lin.resize(w1 + 1, ~0ull);
+            for (size_t w = w0; w <= w1; ++w)
+                if (lin[w] == ~0ull) lin[w] = v0;
+        }
+        std::stable_sort(chunks.begin(), chunks.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+        uint32_t n_bin = 1;
+        for (size_t c = 0; c < chunks.size(); ++c)
+            if (!c || chunks[c].first != chunks[c - 1].first) ++n_bin;
+        put_u32(out, n_bin);
+        for (size_t c = 0; c < chunks.size();) {
+            size_t c1 = c;
+            while (c1 < chunks.size() && chunks[c1].first == chunks[c].first) ++c1;
+            put_u32(out, chunks[c].first);
+            put_u32(out, (uint32_t)(c1 - c));
+            for (; c < c1; ++c) {
+                put_u64(out, chunks[c].second.first);
+                put_u64(out, chunks[c].second.second);
+            }
+        }
+        put_u32(out, 37450);
+        put_u32(out, 2);
+        put_u64(out, voff(b.ent[k0].off));
+        put_u64(out, voff(k < n ? b.ent[k].off : b.stream_len));
+        put_u64(out, n_map);
+        put_u64(out, n_unm);
+        for (size_t w = lin.size(); w-- > 0;)  // unset windows take the next set one's value; the last window is set by the record that made it
+            if (lin[w] == ~0ull) lin[w] = lin[w + 1];
+        put_u32(out, (uint32_t)lin.size());
+        for (uint64_t v : lin) put_u64(out, v);
+    }
+    const uint64_t n_no_coor = n - k;
+    for (; k < n; ++k)
+        if (b.ent[k].ref_id != -1) return "entry " + std::to_string(k) + " lies in front of the entry before it";
+    put_u64(out, n_no_coor);
+    return "";
+}
+}  // namespace
 
 extern "C" uint64_t plo_bam_writer_file_bytes(const plo_bam_writer *w) { return w ? w->file_off : 0; }
 
@@ -1508,6 +1679,19 @@ extern "C" plo_status plo_bam_writer_close(plo_bam_writer *w) {
     }
     if (w->seekable && w->reserved > end && ftruncate(w->fd, (off_t)end) != 0 && st == PLO_OK)  // reserved blocks behind the end go back
         st = fail(PLO_ERR_IO, "ftruncate failed");
+    if (w->bai && st == PLO_OK) {  // the BAM is complete: its index, or the reason there is none
+        std::vector<uint8_t> bai;
+        const std::string why = bai_build(*w->bai, w->n_ref, w->file_off, bai);
+        if (!why.empty()) st = fail(PLO_ERR_INVALID_ARG, "plo_bam_writer_close: no index is written to " + w->bai->path + ": " + why);
+        else {
+            FILE *f = fopen(w->bai->path.c_str(), "wb");
+            const bool ok = f && fwrite(bai.data(), 1, bai.size(), f) == bai.size();
+            if ((f && fclose(f) != 0) || !ok) {
+                ::unlink(w->bai->path.c_str());
+                st = fail(PLO_ERR_IO, "cannot write " + w->bai->path);
+            }
+        }
+    }
     ::close(w->fd);
     delete w;
     return st;
@@ -1565,6 +1749,9 @@ plo_status merge_next(MergeRun &m, uint32_t n_ref) {
 }  // namespace
 
 extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_paths, const char *out_path, int level, int n_threads) {
+    return plo_bam_merge_runs_indexed(paths, n_paths, out_path, nullptr, level, n_threads);
+}
+extern "C" plo_status plo_bam_merge_runs_indexed(const char *const *paths, uint32_t n_paths, const char *out_path, const char *bai_path, int level, int n_threads) {
     if (!paths || !n_paths || !out_path) return fail(PLO_ERR_INVALID_ARG, "plo_bam_merge_runs: at least one run and an output path are required");
     std::vector<MergeRun> runs(n_paths);
     plo_bam_writer *w = nullptr;
@@ -1576,6 +1763,7 @@ extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_pa
             const plo_status c = plo_bam_writer_close(w);
             if (s == PLO_OK && c == PLO_OK) return c;
             ::unlink(out_path);  // a failed merge leaves no file: what was written so far would read as a complete BAM
+            if (bai_path) ::unlink(bai_path);
             if (s == PLO_OK) return c;
         }
         if (s != PLO_OK) g_bam_err = keep;
@@ -1596,6 +1784,16 @@ extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_pa
     const uint32_t n_ref = (uint32_t)r0->names.size();
     plo_status st = plo_bam_writer_open(out_path, r0->text.c_str(), n_ref, r0->name_ptrs.data(), r0->lens.data(), level, std::max(1, n_threads), &w);
     if (st != PLO_OK) return done(st);
+    if (bai_path && (st = plo_bam_writer_index_enable(w, bai_path)) != PLO_OK) return done(st);
+    std::vector<uint8_t> pend;
+    std::vector<plo_index_entry> ents;  // of the records in `pend`, by the scalar rule of index_core.hpp
+    auto flush = [&]() {
+        plo_status s = bai_path ? plo_bam_writer_index_add(w, ents.data(), ents.size()) : PLO_OK;
+        if (s == PLO_OK) s = plo_bam_write(w, pend.data(), pend.size());
+        ents.clear();
+        pend.clear();
+        return s;
+    };
     // a binary heap of run indices by (key, run): the order inside a run is the run's own
     std::vector<uint32_t> heap;
     auto before = [&](uint32_t a, uint32_t b) { return runs[a].key != runs[b].key ? runs[a].key < runs[b].key : a < b; };
@@ -1614,16 +1812,20 @@ extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_pa
         if (runs[i].rec) heap.push_back(i);
     }
     for (size_t k = heap.size() / 2; k-- > 0;) sift_down(k);
-    std::vector<uint8_t> pend;
     const size_t flush_at = (size_t)8 << 20;
     pend.reserve(flush_at + (1u << 20));
     while (!heap.empty()) {
         MergeRun &m = runs[heap[0]];
-        pend.insert(pend.end(), m.rec, m.rec + m.len);
-        if (pend.size() >= flush_at) {
-            if ((st = plo_bam_write(w, pend.data(), pend.size())) != PLO_OK) return done(st);
-            pend.clear();
+        if (bai_path) {
+            plo::IndexEntry e;
+            const int kind = plo::index_entry_scalar(m.rec, m.len, pend.size(), e);
+            if (kind)
+                return done(fail(PLO_ERR_DATA, m.path + ": record " + std::to_string(m.n_read - 1) + " cannot be indexed: " +
+                                                   (kind == plo::INDEX_ERR_CIGAR ? "its CIGAR passes its end" : "it ends behind 2^29")));
+            ents.push_back({e.off, e.ref_id, e.beg, e.end, e.flags});
         }
+        pend.insert(pend.end(), m.rec, m.rec + m.len);
+        if (pend.size() >= flush_at && (st = flush()) != PLO_OK) return done(st);
         if ((st = merge_next(m, n_ref)) != PLO_OK) return done(st);
         if (!m.rec) {
             heap[0] = heap.back();
@@ -1631,6 +1833,6 @@ extern "C" plo_status plo_bam_merge_runs(const char *const *paths, uint32_t n_pa
         }
         if (!heap.empty()) sift_down(0);
     }
-    if (!pend.empty() && (st = plo_bam_write(w, pend.data(), pend.size())) != PLO_OK) return done(st);
+    if (!pend.empty() && (st = flush()) != PLO_OK) return done(st);
     return done(PLO_OK);
 }

@@ -44,6 +44,7 @@
 #include "nm_core.hpp"
 #include "md_core.hpp"
 #include "sort_core.hpp"
+#include "index_core.hpp"
 #include "window_core.hpp"
 #include "bgzf_walk.hpp"
 #include "index_pack.hpp"
@@ -1344,6 +1345,9 @@ __global__ __launch_bounds__(256) void k_sort_copy(DevSort d, const uint32_t *pe
     if (chunk < n_chunks) sort_copy_chunk(d, perm, chunk, wv::lane(), 64);  // (wave-uniform)
 }
 
+// ---- index entries of the sorted records (index_core.hpp): a wave per record, the records grid-strided over the waves; no LDS
+__global__ __launch_bounds__(256) void k_index(DevBai d) { index_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+
 // ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
 // the label table: a thread per contig name
 __global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
@@ -1643,6 +1647,10 @@ struct plo_ctx {
     DevBuf so_key[2], so_idx[2], so_len, so_slen, so_off, so_partial, so_out, so_blk;
     HostBuf h_so;
     hipEvent_t sev[2] = {nullptr, nullptr};
+    // plo_records_index_dev: the entries and its two words (lowest offender << 4 | kind, n_placed)
+    DevBuf bai_entry, bai_blk;
+    HostBuf h_bai;
+    hipEvent_t xev[2] = {nullptr, nullptr};
     bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2001,7 +2009,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
                       &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk,
-                      &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk,
+                      &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -2011,7 +2019,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_so};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_so, &c->h_bai};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2033,6 +2041,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->mev[i]) (void)hipEventDestroy(c->mev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->xev[i]) (void)hipEventDestroy(c->xev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -3641,6 +3651,70 @@ plo_status plo_records_sort_dev(plo_ctx *c, const plo_sort_in *in, plo_sort_out 
     out->perm = perm;
     out->key = (const uint64_t *)d.key[cur];
     out->n_mapped = h[1];
+    return PLO_OK;
+}
+
+// The index entries of the records at in->bytes (index_core.hpp): ONE launch of k_index, a wave per record, at most 2048 workgroups of four
+// waves; the two result words come back behind it, one wait.
+plo_status plo_records_index_dev(plo_ctx *c, const plo_index_in *in, plo_index_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_record = UINT32_MAX;
+    c->err.clear();
+    const uint32_t n = in->n_records;
+    if (n && (!in->bytes || !in->record_off)) {
+        c->err = "plo_index_in: the records and their offsets are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (n > INDEX_MAX_RECORDS || in->n_ref > 0x7fffffffu) {
+        c->err = "plo_records_index_dev: more than 2^27 - 1 records or 2^31 - 1 references";
+        return PLO_ERR_RANGE;
+    }
+    static_assert(sizeof(plo_index_entry) == sizeof(IndexEntry) && offsetof(plo_index_entry, flags) == offsetof(IndexEntry, flags), "plo_index_entry and IndexEntry are one layout");
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 2; ++i)
+        if (!c->xev[i]) HIP_TRY(c, hipEventCreate(&c->xev[i]));
+    HIP_TRY(c, c->bai_entry.ensure((size_t)std::max(1u, n) * sizeof(IndexEntry)));
+    out->entry = c->bai_entry.as<plo_index_entry>();
+    if (!n) return PLO_OK;
+    HIP_TRY(c, c->bai_blk.ensure(16));
+    HIP_TRY(c, c->h_bai.ensure(16));
+    DevBai d;
+    memset(&d, 0, sizeof(d));
+    d.s.bytes = in->bytes;
+    d.s.n_bytes = in->n_bytes;
+    d.s.n = n;
+    d.s.record_off = in->record_off;
+    d.s.n_ref = in->n_ref;
+    d.entry = c->bai_entry.as<IndexEntry>();
+    d.err = c->bai_blk.as<int>();
+    d.n_placed = c->bai_blk.as<unsigned>() + 1;
+    uint32_t *h = c->h_bai.as<uint32_t>();
+    h[0] = (uint32_t)INDEX_NO_RECORD;
+    h[1] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->bai_blk.p, h, 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->xev[0], st));
+    hipLaunchKernelGGL(k_index, dim3(std::min(2048u, (n + 3u) / 4u)), dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->xev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->bai_blk.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)INDEX_NO_RECORD) {
+        static const char *const what[] = {"", "record_off: it must start at 0, not decrease and end at n_bytes", "its length: fewer than the 36 bytes of block_size and the fixed fields",
+                                           "block_size: block_size + 4 differs from the record's length", "refID: outside [-1, n_ref)", "pos: outside [-1, 2^31 - 2]",
+                                           "its CIGAR: 36 + l_read_name + 4 n_cigar_op passes the record's end", "its end: behind 2^29, which a BAM index cannot address",
+                                           "its place: (reference, pos) is lower than the previous record's, the buffer is not coordinate sorted"};
+        out->err_record = h[0] >> 4;
+        out->err_kind = h[0] & 15u;
+        out->entry = nullptr;
+        c->err = "plo_records_index_dev: record " + std::to_string(out->err_record) + " is refused for " + (out->err_kind >= 1 && out->err_kind <= 8 ? what[out->err_kind] : "an unknown reason") +
+                 "; no entry is handed out";
+        return PLO_ERR_INVALID_ARG;
+    }
+    (void)hipEventElapsedTime(&out->index_ms, c->xev[0], c->xev[1]);
+    out->n_records = n;
+    out->n_placed = h[1];
     return PLO_OK;
 }
 

@@ -425,13 +425,40 @@ class PinnedPool:
             self.free.append(t)
 
 
+def _entries_room(nb: int, index_out, n_records: int):
+    """where the plo_index_entry values of a plo_index_out stand behind the `nb` bytes of a window in its page-locked block, and the size
+    of that block: (at, nbytes).  One block from the pool serves both, so an index costs no page-locked allocation of its own.  The
+    index must count the window's `n_records`: the writer sees offsets only and cannot tell that an entry is missing"""
+    if index_out is None:
+        return nb, nb
+    if int(index_out.n_records) != n_records:
+        raise ValueError("the index holds %d entries for a window of %d records" % (int(index_out.n_records), n_records))
+    at = (nb + 7) & ~7
+    return at, at + int(index_out.n_records) * 24
+
+
+def _entries_down(index_out, dev, block, at: int):
+    """the plo_index_entry values of a plo_index_out on their way into `block` at byte `at` (_entries_room; the caller waits for the
+    stream) -> a numpy array of abi.INDEX_ENTRY_DTYPE over the block, good until the block is released, or None without an index"""
+    from .gather import device_view
+
+    if index_out is None:
+        return None
+    n = int(index_out.n_records)
+    if n:
+        block[at:at + n * 24].copy_(device_view(index_out.entry, n * 24, torch.uint8, dev), non_blocking=True)
+    return block.numpy()[at:at + n * 24].view(abi.INDEX_ENTRY_DTYPE)
+
+
 class DeviceRecords:
     """host copy of a plo_records_out: what the writer takes (`bytes`, `n_bytes`) and the counts, as bam.PloRecordBuf has them"""
 
     def __init__(self, ro: abi.PloRecordsOut, pool: Optional[PinnedPool] = None, dev=None, with_offsets: bool = False,
-                 sorted_out: Optional[abi.PloSortOut] = None):
+                 sorted_out: Optional[abi.PloSortOut] = None, index_out: Optional[abi.PloIndexOut] = None):
         """sorted_out: the plo_sort_out of api.Engine.records_sort_dev on `ro` -- its buffer (the same records in coordinate order) and
-        offsets are taken instead of ro's"""
+        offsets are taken instead of ro's.  index_out: the plo_index_out of api.Engine.records_index_dev on the sorted buffer -- its
+        entries come down with the bytes, behind them in the same page-locked block (`index_entries`, what bam.BamWriter.index_add takes;
+        good until release())"""
         from .gather import device_view
 
         self.n_bytes, self.n_records = int(ro.n_bytes), int(ro.n_records)
@@ -440,7 +467,7 @@ class DeviceRecords:
         self._pool = pool
         import time
 
-        nb = max(16, self.n_bytes)
+        at, nb = _entries_room(max(16, self.n_bytes), index_out, self.n_records)
         t0 = time.perf_counter()
         self._block = pool.take(nb) if pool is not None else torch.empty(nb, dtype=torch.uint8, pin_memory=True)
         t1 = time.perf_counter()
@@ -452,6 +479,7 @@ class DeviceRecords:
             off = torch.empty((self.n_records + 1) * 8, dtype=torch.uint8, pin_memory=True)
             off.copy_(device_view(src.record_off, (self.n_records + 1) * 8, torch.uint8, dev), non_blocking=True)
             self.record_off = off.numpy().view(np.uint64)
+        self.index_entries = _entries_down(index_out, dev, self._block, at)
         torch.cuda.current_stream().synchronize()
         self.block_s, self.copy_s = t1 - t0, time.perf_counter() - t1  # the page-locked block (a fresh one is an allocation) / the copy
         self.bytes = self._block.data_ptr()
@@ -471,8 +499,10 @@ class DeviceBlocks:
     bytes the blocks hold.  The record bytes themselves never leave the device."""
     is_blocks = True
 
-    def __init__(self, eng, ro: abi.PloRecordsOut, level: int, pool: Optional[PinnedPool] = None, dev=None, sorted_out: Optional[abi.PloSortOut] = None):
-        """sorted_out: as for DeviceRecords -- the sorted buffer is compressed instead of ro's"""
+    def __init__(self, eng, ro: abi.PloRecordsOut, level: int, pool: Optional[PinnedPool] = None, dev=None, sorted_out: Optional[abi.PloSortOut] = None,
+                 index_out: Optional[abi.PloIndexOut] = None):
+        """sorted_out, index_out: as for DeviceRecords -- the sorted buffer is compressed instead of ro's, the entries come down with the
+        blocks"""
         from .gather import device_view
         import time
 
@@ -481,12 +511,13 @@ class DeviceBlocks:
         bo = eng.bgzf_compress_dev((sorted_out if sorted_out is not None else ro).bytes, int(ro.n_bytes), level)
         self.n_in, self.n_bytes, self.n_blocks, self.bgzf_ms = int(bo.n_in), int(bo.n_bytes), int(bo.n_blocks), float(bo.bgzf_ms)
         self._pool = pool
-        nb = max(16, self.n_bytes)
+        at, nb = _entries_room(max(16, self.n_bytes), index_out, self.n_records)
         t0 = time.perf_counter()
         self._block = pool.take(nb) if pool is not None else torch.empty(nb, dtype=torch.uint8, pin_memory=True)
         t1 = time.perf_counter()
         if self.n_bytes:
             self._block[:self.n_bytes].copy_(device_view(bo.blocks, self.n_bytes, torch.uint8, dev), non_blocking=True)
+        self.index_entries = _entries_down(index_out, dev, self._block, at)
         torch.cuda.current_stream().synchronize()
         self.block_s, self.copy_s = t1 - t0, time.perf_counter() - t1
         self.bytes = self._block.data_ptr()

@@ -72,6 +72,8 @@ class PipelineStats:
     part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
     nm_device_ms: float = 0.0  # emit_nm: HIP-event time of plo_nm_dev (NM:i of the lifted records)
     md_device_ms: float = 0.0  # emit_md: HIP-event time of plo_md_dev (MD:Z of the lifted records: count, scan, emit)
+    index_device_ms: float = 0.0  # index_runs: HIP-event time of plo_records_index_dev (a wave per record of the sorted buffer)
+    index_paths: List[str] = field(default_factory=list)  # index_runs: <run>.bai of every run of out_paths, in the same order
     sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
@@ -87,8 +89,15 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    device_finish: bool = False, read_threads: Optional[int] = None, build_threads: Optional[int] = None,
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
-                   device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False) -> PipelineStats:  # noqa: E501
-    """sorted_runs (default off; needs device_records=True, out_shards must be 1): every window's records are put in coordinate order on
+                   device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False,
+                   index_runs: bool = False) -> PipelineStats:  # noqa: E501
+    """index_runs (default off; needs sorted_runs=True): every run leaves with its BAM index <run>.bai, so that a caller or a viewer opens
+    it as it is.  plo_records_index_dev runs behind plo_records_sort_dev on the sorted buffer (24 bytes a record: where it stands, its
+    reference, [beg, end) from its CIGAR, the unmapped flag, its bin); the entries come down with the window's bytes -- or, with
+    device_bgzf, with its blocks: the host never holds an uncompressed record -- and the run's writer, which notes where every BGZF block
+    starts, writes the index when it closes.  PipelineStats.index_paths lists them beside out_paths; bam.merge_runs(..., index=True)
+    indexes the merged file.  Off, every byte and every file name is what it was.
+    sorted_runs (default off; needs device_records=True, out_shards must be 1): every window's records are put in coordinate order on
     the device (plo_records_sort_dev behind plo_records_build_dev: reference in header order, position, forward before reverse, unmapped
     copies last, ties in input order) and leave as a run file of their own, a complete BAM with an SO:coordinate header, named
     <stem>.r<reader:02d>w<window:06d><ext> after the window's sequence number at its reader -- `out_path` itself is not written.
@@ -149,6 +158,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    if index_runs and not sorted_runs:
+        raise ValueError("index_runs writes the BAM index of every coordinate-sorted run: it needs sorted_runs=True")
     if sorted_runs and not device_records:
         raise ValueError("sorted_runs sorts the records plo_records_build_dev leaves on the device: it needs device_records=True")
     if sorted_runs and int(out_shards) > 1:
@@ -356,11 +367,16 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 srt = eng.records_sort_dev(ro.bytes, ro.n_bytes, ro.n_records, ro.record_off, len(ref_names))
                                 sort_ms = float(srt.sort_ms)
                                 marks.append(("sort", time.perf_counter()))
+                            ixo, index_ms = None, 0.0
+                            if index_runs and srt is not None:
+                                ixo = eng.records_index_dev(srt.bytes, srt.n_bytes, srt.n_records, srt.record_off, len(ref_names))
+                                index_ms = float(ixo.index_ms)
+                                marks.append(("index", time.perf_counter()))
                             if device_bgzf:
-                                rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev, sorted_out=srt)
+                                rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev, sorted_out=srt, index_out=ixo)
                                 marks.append(("bgzf", time.perf_counter() - rb.block_s - rb.copy_s))
                             else:
-                                rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev, sorted_out=srt)
+                                rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev, sorted_out=srt, index_out=ixo)
                             now = time.perf_counter()
                             marks.append(("download: page-locked block", now - rb.copy_s))
                             marks.append(("download: copy", now))
@@ -373,6 +389,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.nm_device_ms += nm_ms
                             st.md_device_ms += md_ms
                             st.sort_device_ms += sort_ms
+                            st.index_device_ms += index_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
                         del up
@@ -453,8 +470,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                 if rb is not None and rb.n_bytes:
                     if sorted_runs:  # the window's run: a complete BAM of its own
                         run_path = "%s.r%02dw%06d%s" % (run_stem, run_id[0], run_id[1], run_ext)
-                        wr = bam.BamWriter(run_path, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads))
+                        wr = bam.BamWriter(run_path, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads),
+                                           index_path=run_path + ".bai" if index_runs else None)
                         out_paths.append(run_path)
+                        if index_runs:
+                            wr.index_add(rb.index_entries)
                     else:
                         wr = wrs[k]
                     if getattr(rb, "is_blocks", False):
@@ -496,9 +516,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     if sorted_runs:
         if not out_paths and not st.errors:  # no output record at all: one header-only run, so that a merge has a header
             out_paths.append("%s.r%02dw%06d%s" % (run_stem, 0, 0, run_ext))
-            bam.BamWriter(out_paths[0], hdr_out, ref_names, ref_lens, level=level, n_threads=1).close()
+            bam.BamWriter(out_paths[0], hdr_out, ref_names, ref_lens, level=level, n_threads=1, index_path=out_paths[0] + ".bai" if index_runs else None).close()
         out_paths.sort()
         st.out_paths = list(out_paths)
+        if index_runs:
+            st.index_paths = [p_ + ".bai" for p_ in out_paths]
     st.out_file_bytes = sum(os.path.getsize(p_) for p_ in out_paths if os.path.exists(p_))
     st.stage_done_s["output closed"] = time.perf_counter() - t0
     if un is not None:

@@ -23,6 +23,10 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_records_sort_dev on the window's records (--sort-out; this leg runs alone): sort_ms beside the window's records_ms, and one
     device-to-device hipMemcpyAsync of n_bytes taken in the same process (the floor of the permuted copy).  perm, key, record_off and the
     bytes are compared with the order computed on the host (numpy, from the definition of the key) before anything is timed
+  - plo_records_index_dev on the window's sorted records (--index-out; this leg runs alone): index_ms beside the window's sort_ms and
+    records_ms, and one device-to-device hipMemcpyAsync of the call's algorithmic read bytes (36 + 4 n_cigar_op a record) taken in the
+    same process; the entries are compared with those computed on the host (numpy, from the rule) before anything is timed.  On the CPU:
+    the writer's close with and without an index, and the merge of the window's two halves with and without one
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -37,11 +41,13 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --nm-out profiles/r12_nm_window.json
     python tools/bench_records.py --reads 50000 --nm-out profiles/r13_nm_window.json --md-out profiles/r13_md_window.json
     python tools/bench_records.py --reads 50000 --sort-out profiles/r14_sort_window.json
+    python tools/bench_records.py --reads 50000 --index-out profiles/r15_index_window.json
 """
 import argparse
 import ctypes as C
 import json
 import os
+import shutil
 import signal
 import statistics
 import subprocess
@@ -599,6 +605,139 @@ def sort_leg(a, win, index, cn, rn, dev):
     return res, bool(same)
 
 
+def index_leg(a, win, index, cn, rn, rl, dev):
+    """ONE window: plo_records_index_dev on the sorted records, against the entries computed on the host and a device-to-device copy of the
+    call's algorithmic bytes; then, on the CPU, the writer's close with and without an index and the merge of the window's two halves with
+    and without one"""
+    import numpy as np
+    import torch
+
+    from portello_amd import api, bam, build, devbatch
+    from portello_amd.gather import device_view
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    out = eng.liftover_batch_dev(ddesc)
+    eng.compact_output_dev(out)
+    eng.finish_batch_dev(ddesc, up.finish_in())
+    eng.sa_segments_dev(sa_in)
+    ro = eng.records_build_dev(ddesc, rin)
+    n, nb, n_ref = int(ro.n_records), int(ro.n_bytes), len(rn)
+    so = eng.records_sort_dev(ro.bytes, nb, n, ro.record_off, n_ref)
+
+    def down(ptr, count, dtype):
+        return device_view(ptr, count * np.dtype(dtype).itemsize, torch.uint8, dev).cpu().numpy().view(dtype) if count else np.zeros(0, dtype)
+
+    # the expected entries, from the rule: fixed fields, the CIGAR's reference length, reg2bin
+    data, off = down(so.bytes, nb, np.uint8), down(so.record_off, n + 1, np.uint64).astype(np.int64)
+    exp = np.zeros(n, abi_entry_dtype())
+    n_ops = 0
+    for i in range(n):
+        p = int(off[i])
+        ref, pos = (int(x) for x in data[p + 4:p + 12].view("<i4"))
+        lrn, ncig, flag = int(data[p + 12]), int(data[p + 16:p + 18].view("<u2")[0]), int(data[p + 18:p + 20].view("<u2")[0])
+        n_ops += ncig
+        unm = (flag >> 2) & 1
+        if ref < 0:
+            exp[i] = (p, -1, -1, 0, unm | (4680 << 16))
+            continue
+        ops = data[p + 36 + lrn:p + 36 + lrn + 4 * ncig].view("<u4")
+        rlen = int((ops >> 4)[np.isin(ops & 15, (0, 2, 3, 7, 8))].sum())
+        beg = max(pos, 0)
+        end = beg + 1 if unm or rlen == 0 else beg + rlen
+        e1, bn = end - 1, 0
+        for sh, base in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+            if beg >> sh == e1 >> sh:
+                bn = base + (beg >> sh)
+                break
+        exp[i] = (p, ref, beg, end, unm | (bn << 16))
+    io = eng.records_index_dev(so.bytes, nb, n, so.record_off, n_ref)
+    got = down(io.entry, 24 * n, np.uint8).view(exp.dtype)
+    same = int(io.n_records) == n and np.array_equal(got, exp) and int(io.n_placed) == int((exp["ref_id"] >= 0).sum())
+    same = same and np.array_equal(down(so.bytes, nb, np.uint8), data)  # the input is unchanged
+    index_ms, wall_ms, sort_ms, rec_ms = [], [], [], []
+    for k in range(a.warmup + a.reps):
+        ro = eng.records_build_dev(ddesc, rin)
+        so = eng.records_sort_dev(ro.bytes, nb, n, ro.record_off, n_ref)
+        t0 = time.perf_counter()
+        io = eng.records_index_dev(so.bytes, nb, n, so.record_off, n_ref)
+        t1 = time.perf_counter()
+        if k >= a.warmup:
+            index_ms.append(float(io.index_ms))
+            wall_ms.append((t1 - t0) * 1e3)
+            sort_ms.append(float(so.sort_ms))
+            rec_ms.append(float(ro.records_ms))
+    algo_read, algo_write = 36 * n + 4 * n_ops, 24 * n
+    src, dst = torch.empty(max(16, algo_read), dtype=torch.uint8, device=dev), torch.empty(max(16, algo_read), dtype=torch.uint8, device=dev)
+    src.zero_()
+    d2d = []
+    for k in range(a.warmup + a.reps):  # read + write of this copy = 2 algo_read >= the call's algo_read + algo_write
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    # the host side, on the CPU: level-0 files of the window's sorted records
+    tmp = tempfile.mkdtemp(prefix="plo_index_host_")
+    hdr = bam.output_header(rn, rl, sort_order="coordinate")
+    half = n // 2
+    cut = int(off[half])
+    host = {}
+
+    def write(path, lo, hi, e_lo, e_hi, indexed):
+        wr = bam.BamWriter(path, hdr, rn, rl, level=0, n_threads=a.threads, index_path=path + ".bai" if indexed else None)
+        if indexed:
+            ent = exp[e_lo:e_hi].copy()
+            ent["off"] -= lo
+            wr.index_add(ent)
+        wr.write(data[lo:hi])
+        t0 = time.perf_counter()
+        wr.close()
+        return (time.perf_counter() - t0) * 1e3
+
+    try:
+        host["writer_close_ms_without_index"] = write(os.path.join(tmp, "plain.bam"), 0, nb, 0, n, False)
+        host["writer_close_ms_with_index"] = write(os.path.join(tmp, "whole.bam"), 0, nb, 0, n, True)
+        host["bai_bytes"] = os.path.getsize(os.path.join(tmp, "whole.bam.bai"))
+        runs = [os.path.join(tmp, "h0.bam"), os.path.join(tmp, "h1.bam")]
+        write(runs[0], 0, cut, 0, half, False)
+        write(runs[1], cut, nb, half, n, False)
+        for name, indexed in (("merge_ms_without_index", False), ("merge_ms_with_index", True), ("merge_ms_without_index_again", False)):
+            t0 = time.perf_counter()
+            bam.merge_runs(runs, os.path.join(tmp, name + ".bam"), n_threads=a.threads, index=indexed)
+            host[name] = (time.perf_counter() - t0) * 1e3
+        host["merged_files_equal"] = open(os.path.join(tmp, "merge_ms_without_index.bam"), "rb").read() == open(os.path.join(tmp, "merge_ms_with_index.bam"), "rb").read()
+        same = same and host["merged_files_equal"]
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "records": n, "n_bytes": nb, "n_ref": n_ref, "n_placed": int(io.n_placed), "cigar_ops": n_ops,
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "equals_host_entries": bool(same), "launches_per_call": 1,
+           "algo_bytes_read": algo_read, "algo_bytes_written": algo_write,
+           "index_ms": stats(index_ms), "index_call_wall_ms": stats(wall_ms), "sort_ms": stats(sort_ms), "records_ms": stats(rec_ms), "d2d_copy_algo_read_bytes_ms": stats(d2d),
+           "index_gbs_algo_read_plus_write": (algo_read + algo_write) / med(index_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * algo_read / med(d2d) / 1e6,
+           "index_over_d2d_copy_time": med(index_ms) / med(d2d), "index_over_sort_time": med(index_ms) / med(sort_ms), "index_over_records_time": med(index_ms) / med(rec_ms),
+           "host_cpu": host,
+           "not_timed": "the entries' download (24 bytes a record, it rides with the window's bytes in the pipeline); end-to-end throughput with index_runs"}
+    return res, bool(same)
+
+
+def abi_entry_dtype():
+    from portello_amd import abi
+
+    return abi.INDEX_ENTRY_DTYPE
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=50_000)
@@ -617,6 +756,7 @@ def main():
     ap.add_argument("--nm-out", default="", help="run the NM leg (plo_nm_dev beside the window's lift, finish and records times, against a device-to-device copy) alone and write its JSON there")
     ap.add_argument("--md-out", default="", help="run the MD leg (plo_md_dev beside the window's nm, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out")
     ap.add_argument("--sort-out", default="", help="run the sort leg (plo_records_sort_dev on the window's records, against the host's expected order and a device-to-device copy of n_bytes) alone and write its JSON there")
+    ap.add_argument("--index-out", default="", help="run the index leg (plo_records_index_dev on the window's sorted records, against the host's entries and a device-to-device copy of its algorithmic bytes; the writer's and the merge's index on the CPU) alone and write its JSON there")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -658,6 +798,15 @@ def main():
             with open(a.cut_out, "w") as fh:
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
+    if a.index_out:
+        ires, ok = index_leg(a, win, index, cn, rn, [int(x.numel()) for x in w.chrom_seq], dev)
+        win.close()
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.index_out)), exist_ok=True)
+        with open(a.index_out, "w") as fh:
+            fh.write(json.dumps(ires, indent=1) + "\n")
+        print(json.dumps(ires))
         sys.exit(0 if ok else 1)
     if a.sort_out:
         sres, ok = sort_leg(a, win, index, cn, rn, dev)
