@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 15 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed */
+#define PLO_API_VERSION 16 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -439,6 +439,45 @@ typedef struct plo_md_out {
 } plo_md_out;
 
 plo_status plo_md_dev(plo_ctx *ctx, const plo_batch_in *in, plo_md_out *out);
+
+/* ---- = / X CIGARs of the lifted records (device-resident, opt-in) ------------------------------------------------
+ * The reads that go in are pbmm2 alignments with '=' and 'X' ops; liftover_read_alignment maps every compared op to M
+ * (src/liftover_read_alignment.rs:103-107) and simplify_alignment_indels pushes M only, so the records that come out carry M alone, and
+ * the reference tool offers no way to put the ops back.  plo_eqx_dev rewrites the CIGAR of every item with status PLO_ITEM_LIFTED from the
+ * same inputs as plo_nm_dev and plo_md_dev.  The rule: walk the item's output CIGAR (the ops plo_records_build_dev writes without this call).
+ * An op with code M, = or X and length L is COMPARED: its L base pairs are classified by plo_nm_dev's pair rule -- c1 the read's 4-bit
+ * code, c2 the reference byte's code in "=ACMGRSVTWYHKDBN" (any other byte 15); a pair matches iff c1 == 0, or c1 == c2 and c1 != 15 (N
+ * against N is X, R against R is =, a read '=' is =, a reference byte outside the table is X unless the read has '=') -- and the op is
+ * replaced by its maximal runs, '=' for a run of matching and 'X' for a run of mismatching pairs, in order.  Runs do not cross op
+ * boundaries (5M5= over ten matching pairs gives 5=5=), so every output op is no longer than the op it came from and its length fits 28
+ * bits; the output has no two adjacent alike ops wherever the input has none, which compress_cigar guarantees for the lift's CIGARs.  A
+ * compared op of length 0 yields nothing.  Every other op (I, D, N, S, H, P, codes 9-15) is copied as it stands, in its place.  Reference
+ * length, read length, pos, bin and item_ref_end therefore do not change.  The bases under X plus the I and D lengths are the item's
+ * plo_nm_dev value; the X positions are the mismatch letters of its plo_md_dev text that do not stand behind '^'.  Example: reference
+ * ACGTACGT from pos, read ACGAACGT, 8M -> 3=1X4=; 2S4M1I3M rewrites only the 4M and the 3M.
+ * Call order and refusals are plo_md_dev's: after plo_liftover_batch_dev (+ plo_compact_output_dev) and plo_finish_batch_dev on the same
+ * context and batch; out of order, sparse or ASCII bases, an index without chrom_seq -> PLO_ERR_INVALID_ARG; a CIGAR past the chromosome
+ * or the read -> PLO_ERR_RANGE by the same check on the device before a base of the step is touched, err_item the LOWEST such item, no
+ * result handed out.  The call is independent of plo_nm_dev and plo_md_dev: alone or with either or both, in any order, none of the three
+ * drops another's result; plo_nm_dev and plo_md_dev go on reading the lift's M CIGAR, so their results are the same either way.
+ * While the context holds a result, plo_records_build_dev takes every lifted record's CIGAR from it: n_cigar_op, the ops in the record,
+ * and bam_write1's rule by the NEW count -- an item whose = / X CIGAR has more than 65535 ops gets the <l_seq>S<ref_len>N placeholder and
+ * its real ops in CG:B,I even where its M CIGAR had fewer.  Everything else in a record is byte for byte what it is without the call.
+ * SA:Z is NOT changed: it keeps the M CIGARs plo_sa_segments_dev wrote (minimap2's and pbmm2's SA fields are summaries in M as well).
+ * Without a result every byte is as before.  The result is dropped by the context's next plo_liftover_batch* (and plo_finish_batch_dev)
+ * call.  Host builders write no = / X.  Two passes over the same bytes (op counts, then ops) with the 64-bit scan of the counts between
+ * them; TWO waits: one for the total that sizes eqx_ops, one behind the emit.  Outputs are owned by the context, valid until its next
+ * plo_liftover_batch* call. */
+typedef struct plo_eqx_out {
+    uint32_t n_items;
+    const uint64_t *item_eqx_off;  /* [n_items + 1] device, in ops; an item that is not LIFTED has length 0 */
+    const uint32_t *eqx_ops;       /* device; BAM-encoded ops (len << 4 | code), the items side by side */
+    uint64_t n_ops;
+    uint32_t err_item;             /* PLO_ERR_RANGE: lowest offending item, UINT32_MAX otherwise */
+    float eqx_ms;                  /* HIP-event time of the call's kernels */
+} plo_eqx_out;
+
+plo_status plo_eqx_dev(plo_ctx *ctx, const plo_batch_in *in, plo_eqx_out *out);
 
 /* ---- BGZF blocks (device-resident) ------------------------------------------------------------------------------
  * Cuts the n_bytes at `bytes` -- any device buffer, typically plo_records_out::bytes -- into payloads of 0xff00 bytes (htslib's

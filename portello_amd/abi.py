@@ -112,7 +112,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 15  # include/portello_liftover.h
+PLO_API_VERSION = 16  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -215,6 +215,10 @@ class PloIndexIn(C.Structure):
 class PloIndexOut(C.Structure):
     _fields_ = [("entry", C.POINTER(PloIndexEntry)), ("n_records", C.c_uint32), ("n_placed", C.c_uint32), ("err_record", C.c_uint32), ("err_kind", C.c_uint32),
                 ("index_ms", C.c_float)]
+
+
+class PloEqxOut(C.Structure):
+    _fields_ = [("n_items", C.c_uint32), ("item_eqx_off", _u64p), ("eqx_ops", _u32p), ("n_ops", C.c_uint64), ("err_item", C.c_uint32), ("eqx_ms", C.c_float)]
 
 
 class PloBgzfOut(C.Structure):

@@ -84,6 +84,8 @@ def load_library(path: Optional[str] = None):
     L.plo_records_sort_dev.argtypes = [vp, C.POINTER(abi.PloSortIn), C.POINTER(abi.PloSortOut)]
     L.plo_records_index_dev.restype = C.c_int
     L.plo_records_index_dev.argtypes = [vp, C.POINTER(abi.PloIndexIn), C.POINTER(abi.PloIndexOut)]
+    L.plo_eqx_dev.restype = C.c_int
+    L.plo_eqx_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloEqxOut)]
     L.plo_records_build_dev.restype = C.c_int
     L.plo_records_build_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloRecordsIn), C.POINTER(abi.PloRecordsOut)]
     L.plo_bgzf_inflate_dev.restype = C.c_int
@@ -270,6 +272,21 @@ class Engine:
         if st != abi.PLO_OK:
             msg = self.lib.plo_last_error(self.handle)
             e = PortelloError(st, f"plo_md_dev: {msg.decode() if msg else ''}")
+            e.err_item = int(out.err_item)
+            raise e
+        return out
+
+    def eqx_dev(self, desc: abi.PloBatchIn) -> abi.PloEqxOut:
+        """The = / X CIGAR of every lifted item of the batch this context has just lifted, compacted and finished (plo_eqx_dev): every M, =
+        or X op of the output CIGAR replaced by its maximal runs of matching (=) and mismatching (X) pairs against the index's chromosomes,
+        every other op as it stands; the items' ops side by side with their offsets, device pointers out.  While the result stands (until
+        the next lift call), records_build_dev writes these CIGARs in place of the lift's.  Independent of nm_dev and md_dev.  A CIGAR that
+        leaves its chromosome or its read raises PortelloError with status PLO_ERR_RANGE and the lowest such item in `err_item`."""
+        out = abi.PloEqxOut()
+        st = self.lib.plo_eqx_dev(self.handle, C.byref(desc), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_eqx_dev: {msg.decode() if msg else ''}")
             e.err_item = int(out.err_item)
             raise e
         return out

@@ -43,6 +43,7 @@
 #include "batch_core.hpp"
 #include "nm_core.hpp"
 #include "md_core.hpp"
+#include "eqx_core.hpp"
 #include "sort_core.hpp"
 #include "index_core.hpp"
 #include "window_core.hpp"
@@ -1309,8 +1310,15 @@ __global__ __launch_bounds__(64) void k_rec_scan_apply(const unsigned long long 
     rec_scan_apply(in + (size_t)blockIdx.y * n, n, blockIdx.x, partial + (size_t)blockIdx.y * nb, out + (size_t)blockIdx.y * ((size_t)n + 1));
 }
 // emit: a workgroup per read at a time.  HBM-bound: per 15 kb record ~22.5 kB in, the same out.  VEC false: the plain byte copy (A/B)
-template <bool VEC>
+template <bool VEC, bool EQX>
 __global__ __launch_bounds__(256) void k_rec_emit(DevBatch bt, DevWork wk, DevRecords d) {
+    // EQX false: the kernel of a context without a plo_eqx_dev result.  That its CIGARs are the lift's is known when it is compiled, and its
+    // code is what it was before the two fields existed (120 VGPRs, 4 waves per SIMD); choosing the CIGAR at run time in the one kernel
+    // made it 141 VGPRs and 3 waves, and records_ms without a result 2.05 ms where it had been 1.82 (EXPERIMENTS 16.5)
+    if (!EQX) {
+        d.item_eqx_off = nullptr;
+        d.eqx_ops = nullptr;
+    }
     for (uint32_t r = blockIdx.x; r < bt.n_reads; r += gridDim.x) records_emit_read<VEC>(bt, wk, d, r, (int)threadIdx.x, (int)blockDim.x);
 }
 
@@ -1322,6 +1330,11 @@ __global__ __launch_bounds__(256) void k_nm(DevBatch bt, DevWork wk, DevNm d) { 
 // the same persistent waves, twice over the same bytes: the lengths of the items' texts, then (behind the 64-bit scan) the texts
 __global__ __launch_bounds__(256) void k_md_count(DevBatch bt, DevWork wk, DevMd d) { md_items<false>(bt, wk, d); }
 __global__ __launch_bounds__(256) void k_md_emit(DevBatch bt, DevWork wk, DevMd d) { md_items<true>(bt, wk, d); }
+
+// ---- = / X CIGARs of the lifted records (eqx_core.hpp) ---------------------------------------------------------------------
+// the same persistent waves, twice over the same bytes: the op counts of the items' CIGARs, then (behind the 64-bit scan) the ops
+__global__ __launch_bounds__(256) void k_eqx_count(DevBatch bt, DevWork wk, DevEqx d) { eqx_items<false>(bt, wk, d); }
+__global__ __launch_bounds__(256) void k_eqx_emit(DevBatch bt, DevWork wk, DevEqx d) { eqx_items<true>(bt, wk, d); }
 
 // ---- the window's records in coordinate order (sort_core.hpp) -------------------------------------------------------------
 // check + keys + the tile sort in LDS (12 KB), a merge launch per doubling of the runs, the lengths in sorted order, and (behind the
@@ -1643,6 +1656,10 @@ struct plo_ctx {
     DevBuf md_len, md_off, md_partial, md_text, md_blk;
     HostBuf h_md;
     hipEvent_t mev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool have_eqx = false;  // plo_eqx_dev's result of the current batch: plo_records_build_dev writes its = / X CIGARs in place of the lift's; dropped like have_nm
+    DevBuf eqx_len, eqx_off, eqx_partial, eqx_ops, eqx_blk;
+    HostBuf h_eqx;
+    hipEvent_t eqev[4] = {nullptr, nullptr, nullptr, nullptr};
     // plo_records_sort_dev: buffers of its own (the sorted copy of the window's bytes, two (key, index) arrays, lengths, offsets)
     DevBuf so_key[2], so_idx[2], so_len, so_slen, so_off, so_partial, so_out, so_blk;
     HostBuf h_so;
@@ -2008,7 +2025,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
-                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk,
+                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk, &c->eqx_len, &c->eqx_off, &c->eqx_partial, &c->eqx_ops, &c->eqx_blk,
                       &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
@@ -2019,7 +2036,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_so, &c->h_bai};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2039,6 +2056,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->nev[i]) (void)hipEventDestroy(c->nev[i]);
     for (int i = 0; i < 4; ++i)
         if (c->mev[i]) (void)hipEventDestroy(c->mev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->eqev[i]) (void)hipEventDestroy(c->eqev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
     for (int i = 0; i < 2; ++i)
@@ -2208,6 +2227,7 @@ plo_status plo_liftover_batch_dev(plo_ctx *c, const plo_batch_in *in, uint32_t s
     c->err.clear();
     c->have_nm = false;
     c->have_md = false;
+    c->have_eqx = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     if (in->n_segs && (!in->seg_read || !in->seg_contig || !in->seg_pos || !in->seg_is_fwd_strand || !in->seg_cigar_off)) {
         c->err = "plo_batch_in: NULL segment array";
@@ -3079,6 +3099,7 @@ plo_status plo_finish_batch_dev(plo_ctx *c, const plo_batch_in *in, const plo_fi
     c->have_sa = false;
     c->have_nm = false;
     c->have_md = false;
+    c->have_eqx = false;
     HIP_TRY(c, hipSetDevice(c->ix->device));
     hipStream_t st = c->stream;
     for (int i = 0; i < 3; ++i)
@@ -3308,6 +3329,8 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     d.item_nm = c->have_nm ? c->nm_out.as<uint32_t>() : nullptr;
     d.item_md_off = c->have_md ? c->md_off.as<uint64_t>() : nullptr;
     d.md_text = c->have_md ? c->md_text.as<uint8_t>() : nullptr;
+    d.item_eqx_off = c->have_eqx ? c->eqx_off.as<uint64_t>() : nullptr;
+    d.eqx_ops = c->have_eqx ? c->eqx_ops.as<uint32_t>() : nullptr;
     d.cs_is_fwd = c->ix->d.cs_is_fwd;
     d.contig_seg_off = c->ix->d.contig_seg_off;
     d.plan = c->r_plan.as<uint32_t>();
@@ -3352,8 +3375,9 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     HIP_TRY(c, hipEventRecord(c->rev[2], st));
     if (n_rec) {
         const uint32_t nblk = std::min<uint32_t>(nr, (uint32_t)c->n_cus * 8u);
-        if (c->rec_bytecopy) hipLaunchKernelGGL(k_rec_emit<false>, dim3(nblk), dim3(256), 0, st, bt, wk, d);
-        else hipLaunchKernelGGL(k_rec_emit<true>, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        if (c->rec_bytecopy) hipLaunchKernelGGL((k_rec_emit<false, true>), dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        else if (d.item_eqx_off) hipLaunchKernelGGL((k_rec_emit<true, true>), dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        else hipLaunchKernelGGL((k_rec_emit<true, false>), dim3(nblk), dim3(256), 0, st, bt, wk, d);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipMemcpyAsync(d.record_off + n_rec, &h[0], 8, hipMemcpyHostToDevice, st));
@@ -3548,6 +3572,109 @@ plo_status plo_md_dev(plo_ctx *c, const plo_batch_in *in, plo_md_out *out) {
     out->md_text = d.md_text;
     out->md_bytes = total;
     c->have_md = true;
+    return PLO_OK;
+}
+
+// The = / X CIGAR of every lifted item (eqx_core.hpp): k_eqx_count, the 64-bit scan of the op counts, a wait for the total and the refusal,
+// k_eqx_emit, a wait behind it (the event time).  Two waits.
+plo_status plo_eqx_dev(plo_ctx *c, const plo_batch_in *in, plo_eqx_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_item = UINT32_MAX;
+    c->err.clear();
+    c->have_eqx = false;
+    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
+        c->err = "plo_eqx_dev: the batch came with sparse or ASCII bases; the ops are written from complete BAM 4-bit bases (PLO_SEQ_BAM4)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
+        c->err = "plo_eqx_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!c->have_finish) {
+        c->err = "plo_eqx_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevIndex &ix = c->ix->d;
+    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
+        c->err = "plo_eqx_dev: the index has no chrom_seq";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const DevWork &wk = c->last_wk;
+    const DevBatch &bt = c->last_bt;
+    const uint32_t n = wk.n_items;
+    if (n > (uint32_t)NM_NO_ITEM) {
+        c->err = "plo_eqx_dev: more than 2^31 - 1 items in one batch";
+        return PLO_ERR_RANGE;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->eqev[i]) HIP_TRY(c, hipEventCreate(&c->eqev[i]));
+    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    HIP_TRY(c, c->eqx_len.ensure((size_t)std::max(1u, n) * 8));
+    HIP_TRY(c, c->eqx_off.ensure(((size_t)n + 1) * 8));
+    HIP_TRY(c, c->eqx_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->eqx_blk.ensure(16));  // err_item, the count pass's ticket, the emit pass's ticket
+    HIP_TRY(c, c->h_eqx.ensure(32));
+    DevEqx d;
+    memset(&d, 0, sizeof(d));
+    d.item_seq_off = c->f_isoff.as<uint64_t>();
+    d.rev_seq = c->f_rseq.as<uint8_t>();
+    d.chrom_seq = ix.chrom_seq;
+    d.chrom_len = ix.chrom_len;
+    d.n_chroms = ix.n_chroms;
+    d.item_len = c->eqx_len.as<unsigned long long>();
+    d.err_item = c->eqx_blk.as<int>();
+    d.ticket = c->eqx_blk.as<unsigned>() + 1;
+    unsigned long long *off = c->eqx_off.as<unsigned long long>();
+    uint32_t *h = c->h_eqx.as<uint32_t>();
+    h[0] = (uint32_t)NM_NO_ITEM;
+    h[1] = h[2] = h[3] = 0;
+    h[4] = h[5] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->eqx_blk.p, h, 16, hipMemcpyHostToDevice, st));
+    // as many waves as stay resident (k_nm's grid: five workgroups of four per CU at up to 96 VGPRs), never more than items
+    const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
+    HIP_TRY(c, hipEventRecord(c->eqev[0], st));
+    if (n) {
+        hipLaunchKernelGGL(k_eqx_count, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, c->eqx_partial.as<unsigned long long>());
+        hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->eqx_partial.as<unsigned long long>(), n, nb, off);
+        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, (const unsigned long long *)c->eqx_partial.as<unsigned long long>(), off);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h + 4, off + n, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(c->eqx_off.p, 0, 8, st));
+    }
+    HIP_TRY(c, hipEventRecord(c->eqev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->eqx_blk.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)NM_NO_ITEM) {
+        out->err_item = h[0];
+        c->err = "plo_eqx_dev: the CIGAR of item " + std::to_string(h[0]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no CIGAR is handed out";
+        return PLO_ERR_RANGE;
+    }
+    const uint64_t total = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
+    HIP_TRY(c, c->eqx_ops.ensure(((size_t)total + 4) * 4));
+    d.item_eqx_off = off;
+    d.eqx_ops = c->eqx_ops.as<uint32_t>();
+    d.ticket = c->eqx_blk.as<unsigned>() + 2;
+    HIP_TRY(c, hipEventRecord(c->eqev[2], st));
+    if (n) {
+        hipLaunchKernelGGL(k_eqx_emit, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->eqev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, c->eqev[0], c->eqev[1]);
+    (void)hipEventElapsedTime(&b, c->eqev[2], c->eqev[3]);
+    out->eqx_ms = a + b;
+    out->n_items = n;
+    out->item_eqx_off = c->eqx_off.as<uint64_t>();
+    out->eqx_ops = d.eqx_ops;
+    out->n_ops = total;
+    c->have_eqx = true;
     return PLO_OK;
 }
 

@@ -9,7 +9,9 @@
 //   emit  (a workgroup per read): every byte of the read's records, the bulk as aligned 16-byte stores
 // With DevRecords::item_nm (nm_core.hpp) every lifted record gets NM:i behind ZM:C.  With DevRecords::item_md_off / md_text (md_core.hpp) it
 // gets MD:Z behind that (calmd appends NM, then MD), and the first field tagged MD of the source record, whatever its type, is cut from the
-// lifted records (the sixth cut; an unmapped copy keeps it).  Those are the two differences to the host builder.
+// lifted records (the sixth cut; an unmapped copy keeps it).  With DevRecords::item_eqx_off / eqx_ops (eqx_core.hpp) the CIGAR of every
+// lifted record -- n_cigar_op, the ops in the record or in CG:B,I, the 65535 rule -- is that result's in place of the lift's.  Those are the
+// three differences to the host builder.
 // The same functions run under the CPU emulator (tests/emu/emu_records.cpp).
 #pragma once
 #include <plo_wave.hpp>
@@ -51,6 +53,8 @@ struct DevRecords {
     const uint32_t *item_nm;  // the context's plo_nm_dev result: NM:i behind ZM:C of every lifted record; NULL: no NM, the host builder's bytes
     const uint64_t *item_md_off;  // the context's plo_md_dev result: MD:Z behind ZM:C / NM:i of every lifted record, the source's first MD cut; NULL: neither
     const uint8_t *md_text;
+    const uint64_t *item_eqx_off;  // the context's plo_eqx_dev result (eqx_core.hpp): the CIGAR of every lifted record with = / X for M, in ops; NULL: wk.out_cigar
+    const uint32_t *eqx_ops;
     // the index: strand of the contig segments (PS suffix)
     const uint8_t *cs_is_fwd;
     const uint32_t *contig_seg_off;
@@ -112,9 +116,17 @@ PLO_DEV unsigned long long aux_field_len_wave(const uint8_t *a, const uint8_t *e
     return 3 + n <= room ? 3 + n : 0;
 }
 
+// the CIGAR item i's record carries: the lift's, or the = / X one of plo_eqx_dev while the context holds it.  bam_write1's 65535 rule goes by this count
+PLO_DEV uint32_t rec_n_cigar(const DevWork &wk, const DevRecords &d, uint32_t i) {
+    return d.item_eqx_off ? (uint32_t)(d.item_eqx_off[i + 1] - d.item_eqx_off[i]) : wk.cig_len[i];
+}
+PLO_DEV const uint32_t *rec_cigar(const DevWork &wk, const DevRecords &d, uint32_t i) {
+    return d.item_eqx_off ? d.eqx_ops + d.item_eqx_off[i] : wk.out_cigar + wk.cig_off[i];
+}
+
 // bytes of a lifted record without its SA tag (records_build's lifted_size): `base` = 4 + 32 + l_qname + bases + qualities + kept aux
 PLO_DEV unsigned long long rec_lifted_size(const DevBatch &bt, const DevWork &wk, const DevRecords &d, uint32_t i, unsigned long long base) {
-    const uint32_t nc = wk.cig_len[i];
+    const uint32_t nc = rec_n_cigar(wk, d, i);
     const uint32_t contig = bt.seg_contig[wk.item_seg[i]];
     unsigned long long sz = base + (nc <= 0xffffu ? 4ull * nc : 8ull + 8ull + 4ull * nc);  // bam_write1: placeholder + CG:B,I
     sz += 3ull + (d.contig_name_off[contig + 1] - d.contig_name_off[contig]) + 6u + dec_digits(wk.item_cseg[i]) + 1u + 1u;  // PS:Z{contig}_split{n}{+|-}\0
@@ -401,8 +413,8 @@ PLO_DEV void records_emit_read(const DevBatch &bt, const DevWork &wk, const DevR
         if (wk.status[i] == PLO_ITEM_LIFTED) sa_total += d.sa_off[i + 1] - d.sa_off[i];
     for (uint32_t i = i0; i < i1; ++i) {
         if (wk.status[i] != PLO_ITEM_LIFTED) continue;
-        const uint32_t nc = wk.cig_len[i];
-        const uint32_t *cg = wk.out_cigar + wk.cig_off[i];
+        const uint32_t nc = rec_n_cigar(wk, d, i);
+        const uint32_t *cg = rec_cigar(wk, d, i);
         const long long pos = wk.pos[i];
         unsigned long long size = rec_lifted_size(bt, wk, d, i, base);
         if (nl > 1) size += 3ull + (sa_total - (d.sa_off[i + 1] - d.sa_off[i])) + 1;

@@ -72,6 +72,7 @@ class PipelineStats:
     part_start_device_ms: float = 0.0  # device_input with part / n_parts: HIP-event time of plo_part_start_dev (the part's first record)
     nm_device_ms: float = 0.0  # emit_nm: HIP-event time of plo_nm_dev (NM:i of the lifted records)
     md_device_ms: float = 0.0  # emit_md: HIP-event time of plo_md_dev (MD:Z of the lifted records: count, scan, emit)
+    eqx_device_ms: float = 0.0  # emit_eqx: HIP-event time of plo_eqx_dev (= / X CIGARs of the lifted records: count, scan, emit)
     index_device_ms: float = 0.0  # index_runs: HIP-event time of plo_records_index_dev (a wave per record of the sorted buffer)
     index_paths: List[str] = field(default_factory=list)  # index_runs: <run>.bai of every run of out_paths, in the same order
     sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
@@ -90,8 +91,14 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
                    device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False,
-                   index_runs: bool = False) -> PipelineStats:  # noqa: E501
-    """index_runs (default off; needs sorted_runs=True): every run leaves with its BAM index <run>.bai, so that a caller or a viewer opens
+                   index_runs: bool = False, emit_eqx: bool = False) -> PipelineStats:  # noqa: E501
+    """emit_eqx (default off; needs device_records=True): every lifted record leaves with a pbmm2-style CIGAR, every M op replaced by its
+    maximal runs of '=' (the read's base matches the reference chromosome of the index, by emit_nm's pair rule) and 'X' (it does not);
+    every other op stays (plo_eqx_dev between the finishing and plo_records_build_dev, which then writes these ops, by bam_write1's rule
+    in CG:B,I where there are more than 65535 of them).  Positions, bins, reference ends and SA:Z, whose CIGARs stay in M, do not
+    change, nor do the unmapped copies.  Combines with emit_nm, emit_md, device_bgzf, sorted_runs and index_runs.  Off, every byte is
+    what it was.
+    index_runs (default off; needs sorted_runs=True): every run leaves with its BAM index <run>.bai, so that a caller or a viewer opens
     it as it is.  plo_records_index_dev runs behind plo_records_sort_dev on the sorted buffer (24 bytes a record: where it stands, its
     reference, [beg, end) from its CIGAR, the unmapped flag, its bin); the entries come down with the window's bytes -- or, with
     device_bgzf, with its blocks: the host never holds an uncompressed record -- and the run's writer, which notes where every BGZF block
@@ -166,6 +173,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         raise ValueError("sorted_runs writes a run file per window: out_shards > 1 has no meaning with it")
     if emit_nm and not device_records:
         raise ValueError("emit_nm counts NM on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
+    if emit_eqx and not device_records:
+        raise ValueError("emit_eqx writes = / X CIGARs on the device, into the records plo_records_build_dev writes: it needs device_records=True")
     if emit_md and not device_records:
         raise ValueError("emit_md writes MD on the device, from the bases and CIGARs plo_records_build_dev writes: it needs device_records=True")
     if device_input and not device_batch:
@@ -360,6 +369,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             if emit_md:
                                 md_ms = float(eng.md_dev(ddesc).md_ms)
                                 marks.append(("md", time.perf_counter()))
+                            eqx_ms = 0.0
+                            if emit_eqx:
+                                eqx_ms = float(eng.eqx_dev(ddesc).eqx_ms)
+                                marks.append(("eqx", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
                             srt, sort_ms = None, 0.0
@@ -388,6 +401,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.records_device_ms += rb.records_ms
                             st.nm_device_ms += nm_ms
                             st.md_device_ms += md_ms
+                            st.eqx_device_ms += eqx_ms
                             st.sort_device_ms += sort_ms
                             st.index_device_ms += index_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)

@@ -20,6 +20,9 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_md_dev on the window (--md-out; runs alone or behind --nm-out): md_ms (count pass, scan, emit pass) beside the same window's nm_ms,
     lift, finish and records_ms event times, the text's bytes and the two passes' algorithmic bytes, and one device-to-device
     hipMemcpyAsync of that many bytes taken in the same process
+  - plo_eqx_dev on the window (--eqx-out; runs alone or behind --nm-out / --md-out): eqx_ms (count pass, scan, emit pass) beside the same
+    window's nm_ms, md_ms, lift, finish and records_ms event times (records_ms without a result and with the eqx result alone), the ops
+    written and the two passes' algorithmic bytes, and one device-to-device hipMemcpyAsync of that many bytes taken in the same process
   - plo_records_sort_dev on the window's records (--sort-out; this leg runs alone): sort_ms beside the window's records_ms, and one
     device-to-device hipMemcpyAsync of n_bytes taken in the same process (the floor of the permuted copy).  perm, key, record_off and the
     bytes are compared with the order computed on the host (numpy, from the definition of the key) before anything is timed
@@ -527,6 +530,92 @@ def md_leg(a, win, index, cn, rn, dev):
     return res, bool(same)
 
 
+def eqx_leg(a, win, index, cn, rn, dev):
+    """ONE window: plo_eqx_dev beside the window's lift, finish, plo_nm_dev, plo_md_dev and records calls (records_ms without a result and
+    with the eqx result alone), and against a device-to-device copy of its algorithmic bytes"""
+    import numpy as np
+    import torch
+
+    from portello_amd import abi, api, build, devbatch
+
+    def arr(ptr, dtype, count):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype) if count else np.zeros(0, dtype)
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    lift_ms, fin_ms, nm_ms, md_ms, eqx_ms, eqx_wall_ms, rec_ms, rec_plain_ms = [], [], [], [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        out = eng.liftover_batch_dev(ddesc)
+        eng.compact_output_dev(out)
+        tm = eng.timing()
+        fo = eng.finish_batch_dev(ddesc, up.finish_in())
+        so = eng.sa_segments_dev(sa_in)
+        plain = eng.records_build_dev(ddesc, rin)  # (no result on the context yet: the host builder's bytes)
+        plain_bytes, plain_ms = int(plain.n_bytes), float(plain.records_ms)
+        t0 = time.perf_counter()
+        eo = eng.eqx_dev(ddesc)
+        t1 = time.perf_counter()
+        ro = eng.records_build_dev(ddesc, rin)  # (the eqx result alone: the same records but for their CIGARs)
+        ro_bytes, ro_ms = int(ro.n_bytes), float(ro.records_ms)
+        no = eng.nm_dev(ddesc)
+        mo = eng.md_dev(ddesc)
+        if k >= a.warmup:
+            lift_ms.append(float(tm.total_ms))
+            fin_ms.append(float(fo.finish_ms) + float(fo.revcomp_ms) + float(so.sa_ms))
+            nm_ms.append(float(no.nm_ms))
+            md_ms.append(float(mo.md_ms))
+            eqx_ms.append(float(eo.eqx_ms))
+            eqx_wall_ms.append((t1 - t0) * 1e3)
+            rec_ms.append(ro_ms)
+            rec_plain_ms.append(plain_ms)
+    lift = devbatch.download(eng, out)
+    lifted = np.flatnonzero(lift.item_status == abi.ITEM_LIFTED)
+    l_seq = arr(b.read_seq_len, np.uint32, int(b.n_reads))[arr(b.seg_read, np.uint32, int(b.n_segs))[lift.item_seg[lifted]]].astype(np.int64)
+    ops = lift.cigar.astype(np.int64)
+    ref_adv = np.where(np.isin(ops & 15, (0, 2, 3, 7, 8)), ops >> 4, 0)
+    csum = np.concatenate([[0], np.cumsum(ref_adv)])
+    o0 = lift.item_cigar_off[lifted].astype(np.int64)
+    o1 = o0 + lift.item_cigar_len[lifted]
+    ref_span = csum[o1] - csum[o0]
+    one_pass = int(((l_seq + 1) // 2).sum() + ref_span.sum() + 4 * int(lift.item_cigar_len[lifted].sum()))
+    n_ops = int(eo.n_ops)
+    algo = 2 * one_pass + 4 * n_ops + 24 * int(lift.n_items)
+    # the records differ by their CIGARs alone: 4 bytes an op, 16 more where the new count passes 65535 and the old one did not
+    new_n = np.diff(eng.download(eo.item_eqx_off, np.uint64, int(eo.n_items) + 1).astype(np.int64))[lifted]
+    old_n = lift.item_cigar_len[lifted].astype(np.int64)
+    size = lambda n: 4 * n + 16 * (n > 0xFFFF)
+    same = ro_bytes == plain_bytes + int((size(new_n) - size(old_n)).sum()) and int(eo.n_items) == lift.n_items and int(new_n.sum()) == n_ops
+    src, dst = torch.empty(algo, dtype=torch.uint8, device=dev), torch.empty(algo, dtype=torch.uint8, device=dev)
+    src.zero_()
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "items": int(lift.n_items), "lifted_items": int(len(lifted)), "cigar_ops_of_lifted": int(old_n.sum()),
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "records_differ_by_their_cigars_alone": bool(same), "eqx_ops": n_ops, "items_past_65535_ops": int((new_n > 0xFFFF).sum()),
+           "algorithmic_bytes": algo,
+           "algorithmic_bytes_note": "2 x ((l_seq + 1) / 2 + reference span + 4 x ops over the lifted items) + 4 x the ops written + 24 x items (count out, offsets in and out)",
+           "eqx_ms": stats(eqx_ms), "eqx_call_wall_ms": stats(eqx_wall_ms), "nm_ms": stats(nm_ms), "md_ms": stats(md_ms), "lift_ms": stats(lift_ms), "finish_sa_ms": stats(fin_ms),
+           "records_with_eqx_ms": stats(rec_ms), "records_without_result_ms": stats(rec_plain_ms), "d2d_copy_same_bytes_ms": stats(d2d),
+           "eqx_gbs": algo / med(eqx_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * algo / med(d2d) / 1e6, "eqx_over_d2d_copy_time": med(eqx_ms) / med(d2d),
+           "eqx_over_md_time": med(eqx_ms) / med(md_ms), "eqx_over_nm_time": med(eqx_ms) / med(nm_ms)}
+    return res, bool(same)
+
+
 def sort_leg(a, win, index, cn, rn, dev):
     """ONE window: plo_records_sort_dev on the records of plo_records_build_dev, against the host's expected order and a device-to-device
     copy of the same bytes"""
@@ -755,6 +844,7 @@ def main():
     ap.add_argument("--part-out", default="", help="run the part leg (plo_part_start_dev and the first cut of part 1 of 2 against plo_bam_open_range) alone and write its JSON there")
     ap.add_argument("--nm-out", default="", help="run the NM leg (plo_nm_dev beside the window's lift, finish and records times, against a device-to-device copy) alone and write its JSON there")
     ap.add_argument("--md-out", default="", help="run the MD leg (plo_md_dev beside the window's nm, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out")
+    ap.add_argument("--eqx-out", default="", help="run the = / X leg (plo_eqx_dev beside the window's nm, md, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out / --md-out")
     ap.add_argument("--sort-out", default="", help="run the sort leg (plo_records_sort_dev on the window's records, against the host's expected order and a device-to-device copy of n_bytes) alone and write its JSON there")
     ap.add_argument("--index-out", default="", help="run the index leg (plo_records_index_dev on the window's sorted records, against the host's entries and a device-to-device copy of its algorithmic bytes; the writer's and the merge's index on the CPU) alone and write its JSON there")
     a = ap.parse_args()
@@ -817,9 +907,9 @@ def main():
             fh.write(json.dumps(sres, indent=1) + "\n")
         print(json.dumps(sres))
         sys.exit(0 if ok else 1)
-    if a.nm_out or a.md_out:
+    if a.nm_out or a.md_out or a.eqx_out:
         ok = True
-        for path_out, leg in ((a.nm_out, nm_leg), (a.md_out, md_leg)):
+        for path_out, leg in ((a.nm_out, nm_leg), (a.md_out, md_leg), (a.eqx_out, eqx_leg)):
             if not path_out:
                 continue
             res, leg_ok = leg(a, win, index, cn, rn, dev)
