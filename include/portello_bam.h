@@ -265,6 +265,21 @@ plo_status plo_phase1_info(const plo_phase1 *ph, uint32_t *n_ref, const char *co
                            uint32_t *segments_clipped, uint32_t *segments_joined, uint32_t *n_records);
 void plo_phase1_free(plo_phase1 *ph);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The reference FASTA (--ref) from a file into device memory (API version 17): plo_fasta_create / _feed / _finish of
+ * portello_liftover.h over the file's bytes, what get_chrom_array (src/main.rs:24-62) gives.  The file is read in pieces of piece_bytes
+ * (0: 16 MiB) through two page-locked buffers, by a thread of its own: the read of piece k + 1 runs under the device's work on piece k.
+ * `want` as for plo_fasta_create (plo_phase1_info's ref_names / ref_lens; NULL: every record).  On PLO_OK and on PLO_ERR_DATA from the
+ * text *out is the loader (plo_fasta_record, plo_fasta_last_error; release it with plo_fasta_destroy, behind every index that borrows its
+ * sequences) and *res what plo_fasta_finish reports; otherwise *out is NULL.
+ *   a file that cannot be opened or read                          PLO_ERR_IO
+ *   a file that starts with the gzip magic 1f 8b                  PLO_ERR_DATA: compressed input (gzip, bgzip) is not read, as the reference
+ *                                                                 (fasta::Reader::new(File), genome_ref.rs:49-52) reads plain text only
+ *   a text the rule refuses, a wanted chromosome missing, twice or of another length      PLO_ERR_DATA; plo_bam_last_error names the
+ *                                                                 chromosome and both lengths in the reference's words (main.rs:38-50)
+ * Both file refusals come before any device is touched. */
+plo_status plo_fasta_load_file(const char *path, const plo_fasta_want *want, uint64_t piece_bytes, int device, plo_fasta **out, plo_fasta_out *res);
+
 const char *plo_bam_last_error(void);
 
 #ifdef __cplusplus

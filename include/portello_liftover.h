@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 16 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev) */
+#define PLO_API_VERSION 17 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -843,6 +843,82 @@ const char *plo_version(void);
 uint32_t plo_api_version(void);
 /* Device self-test of the wavefront primitives (DPP scans, cross-lane reads): 0 = ok. */
 int plo_selftest(int device);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The reference FASTA on the device (API 17): what get_chrom_array (src/main.rs:24-62) and get_genome_ref_from_fasta
+ * (lib/rust-vc-utils/src/genome_ref.rs:43-80) do on the host -- one upper-cased ASCII array per chromosome, in the order of the
+ * assembly->reference header, checked against its lengths -- as a stream compaction in HBM.  Plain text only, as the reference.
+ *
+ * THE RULE (this project's own: the FASTA crate the reference parses with is not pinned here; for well-formed files the rule gives
+ * what the crate documents -- a record per '>' line, id = first white-space-delimited token, sequence lines joined without their
+ * trailing white space, then to_ascii_uppercase):
+ *   Lines end at '\n'; the last line may lack it.
+ *   A line whose first byte is '>' is a header line.  Its id is the bytes behind '>' up to the first space, tab, '\r' or the line end; an
+ *   id may be empty; the rest of the line is ignored, whatever it holds.
+ *   Every other line is a sequence line of the record the last header line opened: '\n', '\r', space and tab are dropped, A-Z is kept,
+ *   a-z is stored upper-cased, and EVERY other byte is refused -- a '>' that is not the first byte of its line, a digit, '*', '-', a
+ *   control byte, a byte >= 0x80.  A base in front of the first header line is refused; dropped bytes there are allowed.  An empty file
+ *   gives zero records; a header line directly followed by another gives a record of length 0.
+ *   Wanted chromosomes: names and lengths in the order the caller wants them (plo_phase1_info's ref_names / ref_lens).  Records whose id
+ *   is not wanted are skipped and never stored (their bytes are still checked).  Without a list every record is kept, in file order.
+ * REFUSALS: PLO_ERR_DATA from plo_fasta_finish, which reports the first of the following (a refused byte also from the feed call that
+ *   meets it and from every feed call behind it):
+ *   1. the lowest refused byte of the text: PLO_FA_ERR_BAD_BYTE or PLO_FA_ERR_NO_HEADER, err_offset = its file offset (found on the
+ *      device by an atomic min, so it does not depend on which wave saw which byte);
+ *   2. else PLO_FA_ERR_DUPLICATE: a wanted id on a second header line -- err_offset = the offset of the lowest such line, err_chrom = its
+ *      place in the list, err_len = the first copy's length.  A DELIBERATE DIFFERENCE: the reference's HashMap::insert
+ *      (genome_ref.rs:51-53) silently keeps the last copy; samtools faidx refuses, and so does this loader;
+ *   3. else the lowest place in the list that is PLO_FA_ERR_MISSING (never seen) or PLO_FA_ERR_LENGTH (err_len = the length found,
+ *      err_offset = its header line; a record longer than wanted stores nothing outside its slot and is counted to its end).
+ *   A refused load hands out no sequence: n_chroms = 0, chrom_seq = NULL.
+ * OUTPUT: one device allocation the object owns.  Chromosome c starts at a 256-byte-aligned offset of it (plo_index_create gives its own
+ *   copies a hipMalloc each), a slot has at least 16 bytes, the gaps and the tail are zero.
+ * The result depends on the bytes alone: not on where the pieces are cut, nor on any launch geometry.
+ * The loader exists before any index does, so it is an object of its own on a device with a private stream and its own workspaces.  An
+ * index created from its pointers (seq_mem = PLO_MEM_DEVICE) BORROWS them: destroy the index first, the plo_fasta after it.
+ * ---------------------------------------------------------------------------------------------------------- */
+enum { PLO_FA_ERR_NONE = 0, PLO_FA_ERR_BAD_BYTE = 1, PLO_FA_ERR_NO_HEADER = 2, PLO_FA_ERR_MISSING = 3, PLO_FA_ERR_LENGTH = 4, PLO_FA_ERR_DUPLICATE = 5 };
+
+typedef struct plo_fasta plo_fasta;
+
+typedef struct plo_fasta_want {
+    uint32_t n;
+    const char *const *names; /* [n] NUL-terminated, no name twice */
+    const int64_t *lens;      /* [n] */
+} plo_fasta_want;
+
+typedef struct plo_fasta_out {
+    uint32_t n_chroms;               /* the wanted list's, or without one the records seen                                   */
+    const int64_t *chrom_len;        /* [n_chroms] host memory of the object                                                  */
+    const uint8_t *const *chrom_seq; /* [n_chroms] host array of DEVICE pointers: plo_index_desc::chrom_seq with PLO_MEM_DEVICE */
+    uint64_t n_records_seen;         /* header lines of the text, wanted or not                                               */
+    uint64_t n_bases;                /* bases of the text, stored or not                                                      */
+    uint64_t text_bytes;
+    float fasta_ms;                  /* HIP-event time of the kernels of all pieces, summed                                   */
+    int32_t err_kind;                /* PLO_FA_ERR_*                                                                          */
+    uint64_t err_offset;
+    uint32_t err_chrom;
+    int64_t err_len;
+} plo_fasta_out;
+
+/* want == NULL: keep every record.  text_bytes_hint: the size of the text when known (sizes the first output allocation of a load
+   without a list, which grows when it has to), 0 otherwise. */
+plo_status plo_fasta_create(const plo_fasta_want *want, uint64_t text_bytes_hint, int device, plo_fasta **out);
+/* The text as consecutive pieces of any size, 0 included, in host memory (page-locked memory is copied by DMA).  Returns once `text` has
+   been read; kernels of the piece may still run on the object's stream. */
+plo_status plo_fasta_feed(plo_fasta *f, const uint8_t *text, uint64_t n_bytes);
+/* The end of the text.  Waits for the stream.  The pointers in `out` stay valid until plo_fasta_destroy. */
+plo_status plo_fasta_finish(plo_fasta *f, plo_fasta_out *out);
+/* Record i of the text in file order (i < n_records_seen, valid after plo_fasta_finish, refused loads included): its id (owned by the
+   object), its length, and its place in the wanted list (-1: not wanted; without a list: i). */
+plo_status plo_fasta_record(const plo_fasta *f, uint64_t i, const char **id, int64_t *len, int32_t *want_index);
+/* Copies n host sequences into device memory the object owns; host_seq[i] == NULL stays NULL.  For plo_index_desc::rev_contig_seq, which
+   seq_mem covers together with chrom_seq: with device chromosomes the reverse contigs have to be device pointers too. */
+plo_status plo_fasta_adopt(plo_fasta *f, uint32_t n, const uint8_t *const *host_seq, const int64_t *len, const uint8_t **dev_out);
+/* Copies `bytes` from device memory of the object (a chromosome, an adopted sequence) to host memory on its stream and waits. */
+plo_status plo_fasta_download(plo_fasta *f, void *host_dst, const void *dev_src, size_t bytes);
+void plo_fasta_destroy(plo_fasta *f);
+const char *plo_fasta_last_error(const plo_fasta *f); /* f == NULL: the calling thread's last plo_fasta_create failure */
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,30 @@ class PloIndexDesc(C.Structure):
     ]
 
 
+# plo_fasta_* (the reference FASTA loaded on the device)
+FA_ERR_NONE, FA_ERR_BAD_BYTE, FA_ERR_NO_HEADER, FA_ERR_MISSING, FA_ERR_LENGTH, FA_ERR_DUPLICATE = 0, 1, 2, 3, 4, 5
+
+
+class PloFastaWant(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("names", C.POINTER(C.c_char_p)), ("lens", _i64p)]
+
+
+class PloFastaOut(C.Structure):
+    _fields_ = [
+        ("n_chroms", C.c_uint32),
+        ("chrom_len", _i64p),
+        ("chrom_seq", _pp),
+        ("n_records_seen", C.c_uint64),
+        ("n_bases", C.c_uint64),
+        ("text_bytes", C.c_uint64),
+        ("fasta_ms", C.c_float),
+        ("err_kind", C.c_int32),
+        ("err_offset", C.c_uint64),
+        ("err_chrom", C.c_uint32),
+        ("err_len", C.c_int64),
+    ]
+
+
 class PloBatchIn(C.Structure):
     _fields_ = [
         ("n_reads", C.c_uint32),
@@ -112,7 +136,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 16  # include/portello_liftover.h
+PLO_API_VERSION = 17  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -394,7 +418,7 @@ class IndexData:
 
         chrom_ptrs = (C.c_void_p * max(1, len(self.chrom_seq)))(*[addr(s) for s in self.chrom_seq])
         rev_ptrs = (C.c_void_p * max(1, self.n_contigs))(*[addr(s) for s in self.rev_contig_seq])
-        self._keep = [chrom_ptrs, rev_ptrs]
+        self._keep = [chrom_ptrs, rev_ptrs] + [k for k in self._keep if not isinstance(k, C.Array)]  # (owners of device sequences stay)
         d.chrom_seq = C.cast(chrom_ptrs, _pp)
         d.rev_contig_seq = C.cast(rev_ptrs, _pp)
         d.seq_mem = self.seq_mem

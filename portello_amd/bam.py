@@ -445,6 +445,20 @@ class Phase1:
                              seg_seq_order_end=cp(d.seg_seq_order_end, np.int64, ns), seg_cigar_off=coff,
                              seg_cigar=cp(d.seg_cigar, np.uint32, int(coff[-1])), chrom_seq=list(chrom_seq), rev_contig_seq=revs)
 
+    def index_data_device(self, ref) -> abi.IndexData:
+        """the index description over a reference loaded on the device (fasta.load_reference with this object's ref_names / ref_lens):
+        chrom_seq are ref's device pointers, the reverse contigs are copied into device memory `ref` owns (seq_mem covers both), and the
+        result keeps `ref` alive: an api.Index built from it borrows ref's memory"""
+        assert list(ref.chrom_len) == list(self.ref_lens), "the reference was not loaded with this index's names and lengths"
+        host = self.index_data([np.zeros(0, np.uint8)] * len(self.ref_lens))
+        d = abi.IndexData(contig_len=host.contig_len, contig_seg_off=host.contig_seg_off, seg_chrom_index=host.seg_chrom_index, seg_pos=host.seg_pos,
+                          seg_is_fwd_strand=host.seg_is_fwd_strand, seg_mapq=host.seg_mapq, seg_seq_order_start=host.seg_seq_order_start,
+                          seg_seq_order_end=host.seg_seq_order_end, seg_cigar_off=host.seg_cigar_off, seg_cigar=host.seg_cigar,
+                          chrom_seq=list(ref.chrom_ptrs), rev_contig_seq=ref.adopt(host.rev_contig_seq),
+                          chrom_len=np.array(ref.chrom_len, dtype=np.int64), seq_mem=abi.MEM_DEVICE)
+        d._keep.append(ref)
+        return d
+
     def close(self):
         if getattr(self, "handle", None):
             lib().plo_phase1_free(self.handle)

@@ -56,6 +56,33 @@ def ref_names(w) -> List[str]:
     return [f"chr{i + 1}" for i in range(len(w.chrom_seq))]
 
 
+def write_reference_fasta(w, path: str, width: int = 60, lower_frac: float = 0.0, crlf: bool = False, seed: int = 5) -> bytes:
+    """the workload's reference as a FASTA file: a record per chromosome named as in ref_names, lines of `width` bases, a fraction
+    lower_frac of the bases soft-masked (lower case) in runs, "\r\n" line ends with crlf.  Returns the bytes written."""
+    rng = np.random.default_rng(seed)
+    eol = b"\r\n" if crlf else b"\n"
+    parts = []
+    for name, s in zip(ref_names(w), w.chrom_seq):
+        seq = (s.cpu().numpy() if hasattr(s, "cpu") else np.asarray(s)).astype(np.uint8).copy()
+        if lower_frac > 0 and seq.size:
+            run = 1 + np.arange(seq.size) // 37  # runs of 37 bases masked together
+            mask = rng.random(int(run[-1]) + 1)[run] < lower_frac
+            letters = (seq >= 65) & (seq <= 90)
+            seq[mask & letters] |= 0x20
+        parts.append(b">" + name.encode() + b" synthetic LN:" + str(seq.size).encode() + eol)
+        full = seq.size // width
+        lines = np.empty((full, width + len(eol)), np.uint8)
+        lines[:, :width] = seq[:full * width].reshape(full, width)
+        lines[:, width:] = np.frombuffer(eol, np.uint8)
+        parts.append(lines.tobytes())
+        if seq.size % width:
+            parts.append(seq[full * width:].tobytes() + eol)
+    text = b"".join(parts)
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return text
+
+
 def write_read_bam(w, path: str, lo: int = 0, hi: Optional[int] = None, level: int = 1, seed: int = 11, n_unmapped: int = 5,
                    n_threads: int = 8, odd_names: bool = False) -> dict:
     """reads [lo, hi) of the workload as a read->contig BAM.  Returns what a checker needs: per-read qnames / quals / aux."""

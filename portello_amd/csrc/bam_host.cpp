@@ -4,6 +4,7 @@
 // published behaviour (third party, absent from the reference tree).
 #include <errno.h>
 #include <chrono>
+#include <future>
 #include <memory>
 #include <sys/uio.h>
 
@@ -56,6 +57,99 @@ static plo_status bam_open_capped(const char *path, int n_threads, int device, s
 extern "C" {
 
 const char *plo_bam_last_error(void) { return g_bam_err.c_str(); }
+
+// ---- the reference FASTA from a file (plo_fasta_*, portello_liftover.h) -------------------------------------------------------------------
+plo_status plo_fasta_load_file(const char *path, const plo_fasta_want *want, uint64_t piece_bytes, int device, plo_fasta **out, plo_fasta_out *res) {
+    if (!path || !out || !res) return PLO_ERR_INVALID_ARG;
+    *out = nullptr;
+    memset(res, 0, sizeof(*res));
+    g_bam_err.clear();
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        g_bam_err = std::string(path) + ": cannot open the reference fasta: " + strerror(errno);
+        return PLO_ERR_IO;
+    }
+    auto fail = [&](plo_status st, const std::string &msg) {
+        g_bam_err = msg;
+        fclose(fp);
+        return st;
+    };
+    unsigned char magic[2] = {0, 0};
+    const size_t got = fread(magic, 1, 2, fp);
+    if (ferror(fp)) return fail(PLO_ERR_IO, std::string(path) + ": cannot read the reference fasta: " + strerror(errno));
+    if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
+        return fail(PLO_ERR_DATA, std::string(path) + ": the reference fasta is gzip / bgzip compressed; only plain text is read (decompress it first)");
+    uint64_t size = 0;
+    if (fseeko(fp, 0, SEEK_END) == 0 && ftello(fp) > 0) size = (uint64_t)ftello(fp);
+    if (fseeko(fp, 0, SEEK_SET) != 0) return fail(PLO_ERR_IO, std::string(path) + ": cannot seek in the reference fasta: " + strerror(errno));
+    if (!piece_bytes) piece_bytes = 16ull << 20;  // (EXPERIMENTS 17.2)
+    piece_bytes = std::min<uint64_t>(piece_bytes, 1ull << 30);
+    plo_fasta *f = nullptr;
+    plo_status st = plo_fasta_create(want, size, device, &f);
+    if (st != PLO_OK) return fail(st, std::string("plo_fasta_create: ") + (st == PLO_ERR_NO_DEVICE ? "no usable HIP device" : plo_fasta_last_error(nullptr)));
+    void *buf[2] = {nullptr, nullptr};
+    auto drop = [&]() {
+        plo_host_free(buf[0]);
+        plo_host_free(buf[1]);
+    };
+    if (plo_host_alloc((size_t)piece_bytes, &buf[0]) != PLO_OK || plo_host_alloc((size_t)piece_bytes, &buf[1]) != PLO_OK) {
+        drop();
+        plo_fasta_destroy(f);
+        return fail(PLO_ERR_OUT_OF_MEMORY, "plo_fasta_load_file: no page-locked memory for the two pieces");
+    }
+    struct Got {
+        size_t n;
+        int err;
+    };
+    auto read_piece = [&](void *dst) {  // a whole piece, or what is left of the file
+        Got g = {0, 0};
+        while (g.n < piece_bytes) {
+            const size_t r = fread((char *)dst + g.n, 1, (size_t)piece_bytes - g.n, fp);
+            g.n += r;
+            if (r == 0) {
+                if (ferror(fp)) g.err = errno ? errno : EIO;
+                break;
+            }
+        }
+        return g;
+    };
+    Got cur = read_piece(buf[0]);
+    int k = 0;
+    bool refused = false;
+    while (cur.n > 0 && !cur.err) {
+        std::future<Got> next = std::async(std::launch::async, read_piece, buf[k ^ 1]);  // piece k + 1 is read while piece k is on the device
+        st = plo_fasta_feed(f, (const uint8_t *)buf[k], cur.n);
+        cur = next.get();
+        k ^= 1;
+        if (st == PLO_ERR_DATA) {
+            refused = true;
+            break;
+        }
+        if (st != PLO_OK) {
+            const std::string msg = std::string("plo_fasta_feed: ") + plo_fasta_last_error(f);
+            drop();
+            plo_fasta_destroy(f);
+            return fail(st, msg);
+        }
+    }
+    if (cur.err && !refused) {
+        const std::string msg = std::string(path) + ": cannot read the reference fasta: " + strerror(cur.err);
+        drop();
+        plo_fasta_destroy(f);
+        return fail(PLO_ERR_IO, msg);
+    }
+    st = plo_fasta_finish(f, res);
+    drop();
+    if (st != PLO_OK && st != PLO_ERR_DATA) {
+        const std::string msg = std::string("plo_fasta_finish: ") + plo_fasta_last_error(f);
+        plo_fasta_destroy(f);
+        return fail(st, msg);
+    }
+    fclose(fp);
+    if (st == PLO_ERR_DATA) g_bam_err = std::string(path) + ": " + plo_fasta_last_error(f);
+    *out = f;
+    return st;
+}
 
 plo_status plo_bam_open(const char *path, int n_threads, plo_bam_reader **out) { return plo_bam_open_device(path, n_threads, -2, out); }
 plo_status plo_bam_open_device(const char *path, int n_threads, int device, plo_bam_reader **out) { return bam_open_capped(path, n_threads, device, 0, out); }

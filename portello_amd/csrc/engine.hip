@@ -46,6 +46,8 @@
 #include "eqx_core.hpp"
 #include "sort_core.hpp"
 #include "index_core.hpp"
+#define PLO_FA_HOST 1
+#include "fasta_core.hpp"
 #include "window_core.hpp"
 #include "bgzf_walk.hpp"
 #include "index_pack.hpp"
@@ -1361,6 +1363,16 @@ __global__ __launch_bounds__(256) void k_sort_copy(DevSort d, const uint32_t *pe
 // ---- index entries of the sorted records (index_core.hpp): a wave per record, the records grid-strided over the waves; no LDS
 __global__ __launch_bounds__(256) void k_index(DevBai d) { index_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
 
+// ---- the reference FASTA (fasta_core.hpp): a wave per tile of FA_TILE bytes, the tiles grid-strided over the waves; no LDS.  HBM-bound by
+// design: the piece is read by k_fa_lines, k_fa_count and k_fa_emit (k_fa_headers leaves the tiles without a header line alone), the bases
+// are written once
+__global__ __launch_bounds__(256) void k_fa_lines(DevFasta d) { fa_lines_tiles(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+__global__ __launch_bounds__(64) void k_fa_states(DevFasta d) { fa_states(d); }
+__global__ __launch_bounds__(256) void k_fa_count(DevFasta d) { fa_tiles<0, false>(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+__global__ __launch_bounds__(256) void k_fa_headers(DevFasta d) { fa_tiles<1, false>(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_fa_emit(DevFasta d) { fa_tiles<2, VEC>(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+
 // ---- the liftover batch (batch_core.hpp) -----------------------------------------------------------------------------------
 // the label table: a thread per contig name
 __global__ __launch_bounds__(256) void k_bb_table(DevBatchBuild d) {
@@ -1624,6 +1636,26 @@ struct plo_index {
     DevIndex d{};
     std::vector<void *> owned;  // device allocations owned by the index
     uint32_t max_segs_per_contig = 0;
+};
+
+// plo_fasta_*: the loader of the reference FASTA (fasta_core.hpp).  An object of its own: it exists before any index does.
+struct plo_fasta {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // count pass, header table, emit
+    bool emit_timed = false;  // ev[4], ev[5] are recorded and not yet read
+    bool byte_stores = false;  // PLO_FASTA_BYTESTORES=1: k_fa_emit<false>, every base a store of its own (the A/B of EXPERIMENTS 17.3)
+    std::string err;
+    FaHost h;
+    DevBuf text, tile_fn, tile_state, cnt, start, partial, blk, hdr, dest;
+    HostBuf h_blk, h_hdr, h_dest;
+    uint8_t *out = nullptr;
+    size_t out_cap = 0;
+    float ms = 0.f;
+    bool finished = false;
+    std::vector<int64_t> o_len;
+    std::vector<const uint8_t *> o_ptr;
+    std::vector<void *> adopted;
 };
 
 struct plo_ctx {
@@ -1911,6 +1943,284 @@ void plo_index_destroy(plo_index *ix) {
     for (void *p : ix->owned) (void)hipFree(p);
     delete ix;
 }
+
+// ---- plo_fasta_*: the reference FASTA (fasta_core.hpp) ---------------------------------------------------------------------------------
+static thread_local std::string g_fasta_err;
+#define FA_TRY(f, call)                                                                 \
+    do {                                                                                \
+        hipError_t _e = (call);                                                         \
+        if (_e != hipSuccess) {                                                         \
+            (f)->err = std::string(#call) + ": " + hipGetErrorString(_e);               \
+            return (_e == hipErrorOutOfMemory) ? PLO_ERR_OUT_OF_MEMORY : PLO_ERR_HIP;   \
+        }                                                                               \
+    } while (0)
+
+static void fasta_release(plo_fasta *f) {
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    for (DevBuf *b : {&f->text, &f->tile_fn, &f->tile_state, &f->cnt, &f->start, &f->partial, &f->blk, &f->hdr, &f->dest}) b->release();
+    for (HostBuf *b : {&f->h_blk, &f->h_hdr, &f->h_dest}) b->release();
+    if (f->out) (void)hipFree(f->out);
+    for (void *p : f->adopted) (void)hipFree(p);
+    for (hipEvent_t e : f->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+}
+
+// the output allocation holds at least `need` bytes: a larger one takes over what the old one holds, the rest of it zero
+static plo_status fasta_out_ensure(plo_fasta *f, size_t need) {
+    if (need <= f->out_cap) return PLO_OK;
+    const size_t cap = ((need + need / 2 + 65536) + 255) & ~(size_t)255;
+    uint8_t *p = nullptr;
+    FA_TRY(f, hipMalloc((void **)&p, cap));
+    hipError_t e = hipMemsetAsync(p, 0, cap, f->stream);
+    if (e == hipSuccess && f->out_cap) e = hipMemcpyAsync(p, f->out, f->out_cap, hipMemcpyDeviceToDevice, f->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        f->err = std::string("plo_fasta: growing the output: ") + hipGetErrorString(e);
+        return PLO_ERR_HIP;
+    }
+    if (f->out) (void)hipFree(f->out);
+    f->out = p;
+    f->out_cap = cap;
+    return PLO_OK;
+}
+
+static std::string fasta_refusal_text(const plo_fasta *f) {
+    const FaHost &h = f->h;
+    const std::string name = (h.err_kind >= FA_ERR_MISSING && h.err_chrom < h.want_name.size()) ? h.want_name[h.err_chrom] : std::string();
+    switch (h.err_kind) {
+    case FA_ERR_BAD_BYTE: return "reference fasta: the byte at offset " + std::to_string(h.err_offset) + " of a sequence line is neither a letter nor white space";
+    case FA_ERR_NO_HEADER: return "reference fasta: the base at offset " + std::to_string(h.err_offset) + " stands in front of the first header line";
+    case FA_ERR_MISSING: return "Chromosome \"" + name + "\" specified in the assembly-to-ref alignment file, but not in the reference fasta";
+    case FA_ERR_LENGTH:
+        return "Chromosome \"" + name + "\" specified with inconsistent length: " + std::to_string(h.want_len[h.err_chrom]) + " in the assembly-to-ref alignment file, and " +
+               std::to_string(h.err_len) + " in the reference fasta";
+    case FA_ERR_DUPLICATE: return "Chromosome \"" + name + "\" has a second header line in the reference fasta, at offset " + std::to_string(h.err_offset) + " (the first copy has length " + std::to_string(h.err_len) + ")";
+    }
+    return std::string();
+}
+
+// one piece of at most FA_MAX_PIECE bytes
+static plo_status fasta_piece(plo_fasta *f, const uint8_t *text, uint32_t n) {
+    hipStream_t st = f->stream;
+    const uint32_t nt = (n + FA_TILE - 1) / FA_TILE, nb = (nt + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK;
+    FA_TRY(f, f->text.ensure(((size_t)n + 15) & ~(size_t)15));
+    FA_TRY(f, f->tile_fn.ensure((size_t)nt * 4));
+    FA_TRY(f, f->tile_state.ensure(((size_t)nt + 1) * 4));
+    FA_TRY(f, f->cnt.ensure((size_t)nt * 16));
+    FA_TRY(f, f->start.ensure(((size_t)nt + 1) * 16));
+    FA_TRY(f, f->partial.ensure((size_t)nb * 16));
+    FA_TRY(f, f->blk.ensure(16));
+    FA_TRY(f, f->h_blk.ensure(64));
+    DevFasta d;
+    memset(&d, 0, sizeof(d));
+    d.text = f->text.as<uint8_t>();
+    d.n = n;
+    d.n_tiles = nt;
+    d.in_state = f->h.state;
+    d.tile_fn = f->tile_fn.as<unsigned>();
+    d.tile_state = f->tile_state.as<unsigned>();
+    d.cnt = f->cnt.as<unsigned long long>();
+    d.start = f->start.as<unsigned long long>();
+    d.err = f->blk.as<int>();
+    d.want_first_base = f->h.recs.empty() ? 1 : 0;
+    d.out = f->out;
+    // h_blk: [0, 1] the two offset words up; then [2, 3] their values, [4] the state behind the piece, [6 .. 9] the bases and header lines
+    int *hb = f->h_blk.as<int>();
+    hb[0] = hb[1] = FA_NONE;
+    const dim3 grid(std::min(4096u, (nt + 3u) / 4u));
+    FA_TRY(f, hipMemcpyAsync(f->text.p, text, n, hipMemcpyHostToDevice, st));
+    FA_TRY(f, hipMemcpyAsync(f->blk.p, hb, 8, hipMemcpyHostToDevice, st));
+    FA_TRY(f, hipEventRecord(f->ev[0], st));
+    hipLaunchKernelGGL(k_fa_lines, grid, dim3(256), 0, st, d);
+    hipLaunchKernelGGL(k_fa_states, dim3(1), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_fa_count, grid, dim3(256), 0, st, d);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 2), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, f->partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(2), dim3(64), 0, st, f->partial.as<unsigned long long>(), nt, nb, d.start);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 2), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, (const unsigned long long *)f->partial.as<unsigned long long>(), d.start);
+    FA_TRY(f, hipGetLastError());
+    FA_TRY(f, hipEventRecord(f->ev[1], st));
+    FA_TRY(f, hipMemcpyAsync(hb + 2, f->blk.p, 8, hipMemcpyDeviceToHost, st));
+    FA_TRY(f, hipMemcpyAsync(hb + 4, d.tile_state + nt, 4, hipMemcpyDeviceToHost, st));
+    FA_TRY(f, hipMemcpyAsync(hb + 6, d.start + nt, 8, hipMemcpyDeviceToHost, st));
+    FA_TRY(f, hipMemcpyAsync(hb + 8, d.start + (size_t)nt + 1 + nt, 8, hipMemcpyDeviceToHost, st));
+    FA_TRY(f, hipStreamSynchronize(st));  // (everything of the pieces in front is through too: their emit, and the copy of their destinations)
+    float ms = 0.f;
+    if (f->emit_timed && hipEventElapsedTime(&ms, f->ev[4], f->ev[5]) == hipSuccess) f->ms += ms;
+    f->emit_timed = false;
+    if (hipEventElapsedTime(&ms, f->ev[0], f->ev[1]) == hipSuccess) f->ms += ms;
+    unsigned long long n_bases = 0, n_hdr64 = 0;
+    memcpy(&n_bases, hb + 6, 8);
+    memcpy(&n_hdr64, hb + 8, 8);
+    const uint32_t n_hdr = (uint32_t)n_hdr64;
+    if (n_hdr) {  // (of a refused piece too: whether its lowest base stands in front of its first header line decides the kind)
+        FA_TRY(f, f->hdr.ensure((size_t)n_hdr * sizeof(FaHeader)));
+        FA_TRY(f, f->h_hdr.ensure((size_t)n_hdr * sizeof(FaHeader)));
+        d.hdr = f->hdr.as<FaHeader>();
+        FA_TRY(f, hipEventRecord(f->ev[2], st));
+        hipLaunchKernelGGL(k_fa_headers, grid, dim3(256), 0, st, d);
+        FA_TRY(f, hipGetLastError());
+        FA_TRY(f, hipEventRecord(f->ev[3], st));
+        FA_TRY(f, hipMemcpyAsync(f->h_hdr.p, f->hdr.p, (size_t)n_hdr * sizeof(FaHeader), hipMemcpyDeviceToHost, st));
+        FA_TRY(f, hipStreamSynchronize(st));
+        if (hipEventElapsedTime(&ms, f->ev[2], f->ev[3]) == hipSuccess) f->ms += ms;
+    }
+    std::vector<FaDest> dest;
+    const bool emit = f->h.piece(text, n, f->h_hdr.as<FaHeader>(), n_hdr, n_bases, (unsigned)hb[4], hb[2], hb[3], dest);
+    if (f->h.err_kind) {
+        f->err = fasta_refusal_text(f);
+        return PLO_ERR_DATA;
+    }
+    if (!emit) return PLO_OK;
+    if (plo_status s = fasta_out_ensure(f, (size_t)f->h.out_bytes)) return s;
+    FA_TRY(f, f->dest.ensure(dest.size() * sizeof(FaDest)));
+    FA_TRY(f, f->h_dest.ensure(dest.size() * sizeof(FaDest)));
+    memcpy(f->h_dest.p, dest.data(), dest.size() * sizeof(FaDest));
+    d.dest = f->dest.as<FaDest>();
+    d.out = f->out;
+    FA_TRY(f, hipMemcpyAsync(f->dest.p, f->h_dest.p, dest.size() * sizeof(FaDest), hipMemcpyHostToDevice, st));
+    FA_TRY(f, hipEventRecord(f->ev[4], st));
+    if (f->byte_stores) hipLaunchKernelGGL(k_fa_emit<false>, grid, dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(k_fa_emit<true>, grid, dim3(256), 0, st, d);
+    FA_TRY(f, hipGetLastError());
+    FA_TRY(f, hipEventRecord(f->ev[5], st));
+    f->emit_timed = true;
+    return PLO_OK;
+}
+
+plo_status plo_fasta_create(const plo_fasta_want *want, uint64_t text_bytes_hint, int device, plo_fasta **out) {
+    if (!out) return PLO_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (want && want->n && (!want->names || !want->lens)) {
+        g_fasta_err = "plo_fasta_want: names and lens are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PLO_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return PLO_ERR_NO_DEVICE;
+    plo_fasta *f = new plo_fasta();
+    f->device = device;
+    if (const char *e = getenv("PLO_FASTA_BYTESTORES")) f->byte_stores = atoi(e) != 0;
+    if (want && !f->h.init(want->n, want->names, want->lens)) {
+        g_fasta_err = "plo_fasta_want: a name is NULL or stands twice, or a length is negative";
+        delete f;
+        return PLO_ERR_INVALID_ARG;
+    }
+    plo_status s = PLO_OK;
+    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) s = PLO_ERR_HIP;
+    for (int i = 0; i < 6 && s == PLO_OK; ++i)
+        if (hipEventCreate(&f->ev[i]) != hipSuccess) s = PLO_ERR_HIP;
+    // with a list: the slots, once and for all; without: the text's size is an upper bound of the bases, the slots' padding grows it
+    if (s == PLO_OK) s = fasta_out_ensure(f, want ? std::max<size_t>((size_t)f->h.out_bytes, 256) : (size_t)text_bytes_hint + 4096);
+    if (s != PLO_OK) {
+        g_fasta_err = f->err.empty() ? "plo_fasta_create: no stream or event" : f->err;
+        fasta_release(f);
+        return s;
+    }
+    *out = f;
+    return PLO_OK;
+}
+
+plo_status plo_fasta_feed(plo_fasta *f, const uint8_t *text, uint64_t n_bytes) {
+    if (!f || (n_bytes && !text)) return PLO_ERR_INVALID_ARG;
+    if (f->finished) {
+        f->err = "plo_fasta_feed: the load is finished";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (f->h.err_kind) return PLO_ERR_DATA;
+    if (hipSetDevice(f->device) != hipSuccess) return PLO_ERR_NO_DEVICE;
+    for (uint64_t at = 0; at < n_bytes;) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(n_bytes - at, FA_MAX_PIECE);
+        if (plo_status s = fasta_piece(f, text + at, n)) return s;
+        at += n;
+    }
+    return PLO_OK;
+}
+
+plo_status plo_fasta_finish(plo_fasta *f, plo_fasta_out *out) {
+    if (!f || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    if (hipSetDevice(f->device) != hipSuccess) return PLO_ERR_NO_DEVICE;
+    if (!f->finished) {
+        FA_TRY(f, hipStreamSynchronize(f->stream));
+        float ms = 0.f;
+        if (f->emit_timed && hipEventElapsedTime(&ms, f->ev[4], f->ev[5]) == hipSuccess) f->ms += ms;
+        f->emit_timed = false;
+        f->finished = true;
+        if (f->h.finish()) {
+            f->err = fasta_refusal_text(f);
+        } else {
+            if (plo_status s = fasta_out_ensure(f, (size_t)f->h.out_bytes)) return s;
+            if (f->h.has_want) {
+                for (size_t w = 0; w < f->h.want_name.size(); ++w) {
+                    f->o_len.push_back(f->h.want_len[w]);
+                    f->o_ptr.push_back(f->out + f->h.want_dst[w]);
+                }
+            } else {
+                for (const FaRec &r : f->h.recs) {
+                    f->o_len.push_back(r.len);
+                    f->o_ptr.push_back(f->out + r.dst);
+                }
+            }
+        }
+    }
+    const FaHost &h = f->h;
+    out->n_records_seen = h.recs.size();
+    out->n_bases = h.n_bases;
+    out->text_bytes = h.file_off;
+    out->fasta_ms = f->ms;
+    out->err_kind = h.err_kind;
+    out->err_offset = h.err_offset;
+    out->err_chrom = h.err_chrom;
+    out->err_len = h.err_len;
+    if (h.err_kind) return PLO_ERR_DATA;
+    out->n_chroms = (uint32_t)f->o_len.size();
+    out->chrom_len = f->o_len.data();
+    out->chrom_seq = f->o_ptr.data();
+    return PLO_OK;
+}
+
+plo_status plo_fasta_record(const plo_fasta *f, uint64_t i, const char **id, int64_t *len, int32_t *want_index) {
+    if (!f || !f->finished || i >= f->h.recs.size()) return PLO_ERR_INVALID_ARG;
+    const FaRec &r = f->h.recs[(size_t)i];
+    if (id) *id = r.id.c_str();
+    if (len) *len = r.len;
+    if (want_index) *want_index = r.want;
+    return PLO_OK;
+}
+
+plo_status plo_fasta_adopt(plo_fasta *f, uint32_t n, const uint8_t *const *host_seq, const int64_t *len, const uint8_t **dev_out) {
+    if (!f || (n && (!host_seq || !len || !dev_out))) return PLO_ERR_INVALID_ARG;
+    if (hipSetDevice(f->device) != hipSuccess) return PLO_ERR_NO_DEVICE;
+    for (uint32_t i = 0; i < n; ++i) {
+        dev_out[i] = nullptr;
+        if (!host_seq[i]) continue;
+        if (len[i] < 0) return PLO_ERR_INVALID_ARG;
+        void *p = nullptr;
+        FA_TRY(f, hipMalloc(&p, std::max<size_t>((size_t)len[i], 16)));
+        f->adopted.push_back(p);
+        if (len[i] > 0) FA_TRY(f, hipMemcpy(p, host_seq[i], (size_t)len[i], hipMemcpyHostToDevice));
+        dev_out[i] = (const uint8_t *)p;
+    }
+    return PLO_OK;
+}
+
+plo_status plo_fasta_download(plo_fasta *f, void *host_dst, const void *dev_src, size_t bytes) {
+    if (!f || (bytes && (!host_dst || !dev_src))) return PLO_ERR_INVALID_ARG;
+    if (hipSetDevice(f->device) != hipSuccess) return PLO_ERR_NO_DEVICE;
+    if (bytes) FA_TRY(f, hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, f->stream));
+    FA_TRY(f, hipStreamSynchronize(f->stream));
+    return PLO_OK;
+}
+
+void plo_fasta_destroy(plo_fasta *f) {
+    if (f) fasta_release(f);
+}
+
+const char *plo_fasta_last_error(const plo_fasta *f) { return f ? f->err.c_str() : g_fasta_err.c_str(); }
 
 plo_status plo_index_segment_map(const plo_index *ix, uint32_t g, uint32_t cap, int64_t *keys, int64_t *vals, uint32_t *n) {
     if (!ix || !n || g >= ix->d.n_segments) return PLO_ERR_INVALID_ARG;
