@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 17 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file */
+#define PLO_API_VERSION 18 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file; 18: plo_runs_merge_plan_dev / plo_runs_merge_emit_dev (sorted windows merged into large runs on the device) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -588,6 +588,77 @@ typedef struct plo_index_out {
 } plo_index_out;
 
 plo_status plo_records_index_dev(plo_ctx *ctx, const plo_index_in *in, plo_index_out *out);
+
+/* ---- Sorted windows merged into large runs (device-resident, opt-in; API version 18) --------------------------------------
+ * A k-way merge of coordinate-sorted record buffers -- typically copies of plo_sort_out::bytes / record_off of several windows -- that each
+ * lie in an allocation of their own: a plan, then an emit per chunk of the merged stream, on one context.
+ * The order is plo_records_sort_dev's.  Number the records run-major, g = run_first[r] + place; the merged order is the pair (key, g) with
+ * that call's key.  The pair is unique, so the result is fully determined; it is what plo_records_sort_dev gives over the runs'
+ * concatenation, byte for byte, and what plo_bam_merge_runs gives over the same runs as files, record for record.
+ * plo_runs_merge_plan_dev.  Checked on the device before a byte of a record is trusted, per run, kinds in err_kind:
+ *   1 .. 5  what plo_records_sort_dev checks, in its order, against the run's own record_off and n_bytes: record_off[0] == 0, not
+ *           decreasing, ends at n_bytes; the 36 bytes; block_size; refID in [-1, n_ref); pos
+ *   6       the record's key is lower than the key of the record before it in the same run: the run is not sorted
+ * Any -> PLO_ERR_INVALID_ARG: err_run / err_record (the place in that run) name the LOWEST g that breaks something, err_kind the first kind
+ * it breaks; no result is handed out, plo_last_error names all three.  n_runs == 0 or no record at all -> PLO_OK with empty outputs
+ * (record_off[0] == 0, n_chunks == 0).  n_runs > PLO_MERGE_MAX_RUNS, chunk_bytes == 0, a NULL `runs` with n_runs > 0, a run with records
+ * and a NULL pointer, or a run without records and n_bytes != 0 -> PLO_ERR_INVALID_ARG; more than 2^32 - 2 records in all -> PLO_ERR_RANGE.
+ * A run may be empty, and its pointers may then be NULL.
+ * Chunks: chunk c begins at merged record chunk_first[c] and holds as many following records as keep its bytes <= chunk_bytes, but never
+ * fewer than one.  The table is made on the device and copied down in the call's ONE wait; chunk_first and chunk_off are HOST arrays.
+ * Kernels: keys (a thread per record), a rank launch per doubling of the groups of runs (ceil(log2(n_runs)) of them), gather, the 64-bit
+ * scan (3), chunks (one lane).  Buffers, the call's own, grown to the largest plan and freed with the context: 50 n_records + 8 bytes,
+ * the descriptor table and the chunk table; no record byte is moved.
+ * plo_runs_merge_emit_dev copies the records of chunk `chunk` of the context's current plan, in merged order, into a buffer of the call's own
+ * (grown to the largest chunk) and hands out record_off rebased to the chunk: the shapes plo_records_index_dev and plo_bgzf_compress_dev
+ * take.  One launch, one wait: a wave per 16 KB of the chunk finds the records that reach into its piece and reads each from
+ * runs[r].bytes + runs[r].record_off[place]; every output byte is stored exactly once.  PLO_ERR_INVALID_ARG without a plan (none yet, the
+ * last one refused) or for chunk >= n_chunks.
+ * Two rules.  The runs -- bytes and record_off -- must stay valid and unchanged from the plan to the last emit.  A chunk is valid until the
+ * context's next emit; the plan's outputs until the context's next plan.  The inputs and every other result on the context stay untouched. */
+#define PLO_MERGE_MAX_RUNS 4096
+
+typedef struct plo_merge_run {
+    const uint8_t *bytes;         /* device: the run's records in coordinate order, each prefixed by its block_size */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    const uint64_t *record_off;   /* device [n_records + 1], counted from the run's own `bytes` */
+} plo_merge_run;
+
+typedef struct plo_merge_in {
+    const plo_merge_run *runs;    /* HOST [n_runs] */
+    uint32_t n_runs;
+    uint32_t n_ref;               /* @SQ count of the output header */
+    uint64_t chunk_bytes;         /* the most bytes of a chunk that holds more than one record */
+} plo_merge_in;
+
+typedef struct plo_merge_out {
+    uint32_t n_records;
+    uint32_t n_mapped;            /* records with refID >= 0; the refID -1 tail begins at this merged position */
+    uint64_t n_bytes;
+    const uint32_t *src;          /* device [n_records]: merged position j holds record g = src[j] */
+    const uint64_t *key;          /* device [n_records]: the merged keys */
+    const uint64_t *record_off;   /* device [n_records + 1], of the merged stream */
+    uint32_t n_chunks;
+    const uint32_t *chunk_first;  /* HOST [n_chunks + 1]: chunk c is the merged records [chunk_first[c], chunk_first[c + 1]) */
+    const uint64_t *chunk_off;    /* HOST [n_chunks + 1]: record_off[chunk_first[c]] */
+    uint32_t err_run;             /* PLO_ERR_INVALID_ARG from the device check: the run of the lowest offending g, else UINT32_MAX */
+    uint32_t err_record;          /* its place in that run, else UINT32_MAX */
+    uint32_t err_kind;            /* what it broke (1 .. 6 above), else 0 */
+    float plan_ms;                /* HIP-event time of the call's kernels */
+} plo_merge_out;
+
+typedef struct plo_merge_chunk_out {
+    const uint8_t *bytes;         /* device: the chunk's records in merged order, densely packed */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    uint32_t first_record;        /* chunk_first[chunk] */
+    const uint64_t *record_off;   /* device [n_records + 1], counted from the chunk's first byte */
+    float emit_ms;                /* HIP-event time of the call's kernel */
+} plo_merge_chunk_out;
+
+plo_status plo_runs_merge_plan_dev(plo_ctx *ctx, const plo_merge_in *in, plo_merge_out *out);
+plo_status plo_runs_merge_emit_dev(plo_ctx *ctx, uint32_t chunk, plo_merge_chunk_out *out);
 
 /* ---- The liftover batch (device-resident) ------------------------------------------------------------------------
  * Builds the plo_batch_in / plo_finish_in of a window from its records as they stand in device memory: what plo_bam_window_batch_raw

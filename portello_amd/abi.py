@@ -136,7 +136,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 17  # include/portello_liftover.h
+PLO_API_VERSION = 18  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -222,6 +222,29 @@ class PloSortIn(C.Structure):
 class PloSortOut(C.Structure):
     _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p), ("perm", _u32p), ("key", _u64p),
                 ("n_mapped", C.c_uint32), ("err_record", C.c_uint32), ("sort_ms", C.c_float)]
+
+
+PLO_MERGE_MAX_RUNS = 4096
+
+
+class PloMergeRun(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p)]
+
+
+class PloMergeIn(C.Structure):
+    _fields_ = [("runs", C.POINTER(PloMergeRun)), ("n_runs", C.c_uint32), ("n_ref", C.c_uint32), ("chunk_bytes", C.c_uint64)]
+
+
+class PloMergeOut(C.Structure):
+    """chunk_first / chunk_off are HOST arrays of n_chunks + 1 values, the rest device pointers"""
+    _fields_ = [("n_records", C.c_uint32), ("n_mapped", C.c_uint32), ("n_bytes", C.c_uint64), ("src", _u32p), ("key", _u64p), ("record_off", _u64p),
+                ("n_chunks", C.c_uint32), ("chunk_first", _u32p), ("chunk_off", _u64p), ("err_run", C.c_uint32), ("err_record", C.c_uint32),
+                ("err_kind", C.c_uint32), ("plan_ms", C.c_float)]
+
+
+class PloMergeChunkOut(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("first_record", C.c_uint32), ("record_off", _u64p),
+                ("emit_ms", C.c_float)]
 
 
 class PloIndexEntry(C.Structure):

@@ -82,6 +82,10 @@ def load_library(path: Optional[str] = None):
     L.plo_md_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloMdOut)]
     L.plo_records_sort_dev.restype = C.c_int
     L.plo_records_sort_dev.argtypes = [vp, C.POINTER(abi.PloSortIn), C.POINTER(abi.PloSortOut)]
+    L.plo_runs_merge_plan_dev.restype = C.c_int
+    L.plo_runs_merge_plan_dev.argtypes = [vp, C.POINTER(abi.PloMergeIn), C.POINTER(abi.PloMergeOut)]
+    L.plo_runs_merge_emit_dev.restype = C.c_int
+    L.plo_runs_merge_emit_dev.argtypes = [vp, C.c_uint32, C.POINTER(abi.PloMergeChunkOut)]
     L.plo_records_index_dev.restype = C.c_int
     L.plo_records_index_dev.argtypes = [vp, C.POINTER(abi.PloIndexIn), C.POINTER(abi.PloIndexOut)]
     L.plo_eqx_dev.restype = C.c_int
@@ -328,6 +332,37 @@ class Engine:
             e = PortelloError(st, f"plo_records_index_dev: {msg.decode() if msg else ''}")
             e.err_record, e.err_kind = int(out.err_record), int(out.err_kind)
             raise e
+        return out
+
+    def runs_merge_plan_dev(self, runs, n_ref: int, chunk_bytes: int) -> abi.PloMergeOut:
+        """The merged order of coordinate-sorted record buffers that each lie in a DEVICE allocation of their own (plo_runs_merge_plan_dev).
+        runs: a sequence of (bytes_ptr, n_bytes, n_records, record_off_ptr), record_off counted from the run's own bytes; a run without
+        records may carry 0 for both pointers.  The order is records_sort_dev's over the runs' concatenation: by (key, run, place in the
+        run).  Out: device src / key / record_off of the merged stream and the chunk table as HOST arrays (chunk c holds the merged
+        records [chunk_first[c], chunk_first[c + 1]): as many as keep its bytes <= chunk_bytes, never fewer than one), all valid until the
+        engine's next runs_merge_plan_dev.  No record byte is moved: runs_merge_emit_dev copies a chunk, and the runs must stay valid and
+        unchanged until the last emit.  A record the device check refuses raises PortelloError with status PLO_ERR_INVALID_ARG and
+        `err_run`, `err_record` (its place in that run) and `err_kind` (1 .. 5 as records_sort_dev, 6: a key below the one before it)."""
+        runs = list(runs)
+        arr = (abi.PloMergeRun * max(1, len(runs)))()
+        for k, (b, nb, n, off) in enumerate(runs):
+            arr[k] = abi.PloMergeRun(C.cast(b, abi._u8p), int(nb), int(n), C.cast(off, abi._u64p))
+        min_ = abi.PloMergeIn(arr, len(runs), int(n_ref), int(chunk_bytes))
+        out = abi.PloMergeOut()
+        st = self.lib.plo_runs_merge_plan_dev(self.handle, C.byref(min_), C.byref(out))
+        if st != abi.PLO_OK:
+            msg = self.lib.plo_last_error(self.handle)
+            e = PortelloError(st, f"plo_runs_merge_plan_dev: {msg.decode() if msg else ''}")
+            e.err_run, e.err_record, e.err_kind = int(out.err_run), int(out.err_record), int(out.err_kind)
+            raise e
+        return out
+
+    def runs_merge_emit_dev(self, chunk: int) -> abi.PloMergeChunkOut:
+        """Chunk `chunk` of the engine's current plan copied, in merged order, into a buffer of the context's own (plo_runs_merge_emit_dev):
+        device bytes and record_off rebased to the chunk -- what records_index_dev and bgzf_compress_dev take --, valid until the engine's
+        next runs_merge_emit_dev.  PLO_ERR_INVALID_ARG without a plan or for chunk >= n_chunks."""
+        out = abi.PloMergeChunkOut()
+        self._check(self.lib.plo_runs_merge_emit_dev(self.handle, int(chunk), C.byref(out)), "plo_runs_merge_emit_dev")
         return out
 
     def batch_build_dev(self, bin_: abi.PloBatchBuildIn) -> abi.PloBatchBuildOut:

@@ -45,6 +45,7 @@
 #include "md_core.hpp"
 #include "eqx_core.hpp"
 #include "sort_core.hpp"
+#include "merge_core.hpp"
 #include "index_core.hpp"
 #define PLO_FA_HOST 1
 #include "fasta_core.hpp"
@@ -1360,6 +1361,30 @@ __global__ __launch_bounds__(256) void k_sort_copy(DevSort d, const uint32_t *pe
     if (chunk < n_chunks) sort_copy_chunk(d, perm, chunk, wv::lane(), 64);  // (wave-uniform)
 }
 
+// ---- sorted windows merged into large runs (merge_core.hpp): no LDS anywhere, the runs arrive sorted ---------------------------------------
+// check + keys (a thread per record), a rank launch per doubling of the groups of runs, the lengths in merged order, and (behind the 64-bit
+// scan) the chunk table by one lane.  The emit -- a wave per 16 KB of the chunk's output -- is the only kernel that touches the records' bytes
+__global__ __launch_bounds__(256) void k_merge_keys(DevMerge d) {
+    const unsigned long long g = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (g < d.n) merge_key_record(d, (uint32_t)g);
+}
+__global__ __launch_bounds__(256) void k_merge_rank(DevMerge d, const unsigned long long *sk, const uint32_t *ss, unsigned long long *dk, uint32_t *ds, uint32_t t) {
+    const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (p < d.n) merge_rank_pair(d, sk, ss, dk, ds, t, (uint32_t)p);
+}
+__global__ __launch_bounds__(256) void k_merge_gather(DevMerge d, const uint32_t *src) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (j < d.n) merge_gather(d, src, (uint32_t)j);
+}
+__global__ __launch_bounds__(64) void k_merge_chunks(DevMerge d, const unsigned long long *key) {
+    if (threadIdx.x == 0) merge_chunks(d, key);
+}
+__global__ __launch_bounds__(256) void k_merge_copy(DevMergeEmit d, unsigned long long n_pieces) {
+    const unsigned long long w = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id(), nw = (unsigned long long)gridDim.x * 4u;
+    if (w < n_pieces) merge_copy_piece(d, w, wv::lane(), 64);  // (wave-uniform)
+    merge_rebase(d, w * 64u + (unsigned long long)wv::lane(), nw * 64u);
+}
+
 // ---- index entries of the sorted records (index_core.hpp): a wave per record, the records grid-strided over the waves; no LDS
 __global__ __launch_bounds__(256) void k_index(DevBai d) { index_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
 
@@ -1696,6 +1721,15 @@ struct plo_ctx {
     DevBuf so_key[2], so_idx[2], so_len, so_slen, so_off, so_partial, so_out, so_blk;
     HostBuf h_so;
     hipEvent_t sev[2] = {nullptr, nullptr};
+    // plo_runs_merge_plan_dev / _emit_dev: the plan (two (key, g) arrays, runs, lengths, offsets, the tables) and the current chunk
+    DevBuf mg_key[2], mg_src[2], mg_runof, mg_len, mg_mlen, mg_off, mg_partial, mg_runs, mg_first, mg_blk, mg_cfirst, mg_coff, mg_out, mg_ooff;
+    HostBuf h_mg, h_mg_tab;
+    hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool have_plan = false;
+    int mg_cur = 0;
+    uint32_t mg_n = 0, mg_n_chunks = 0;
+    std::vector<uint32_t> mg_chunk_first;
+    std::vector<uint64_t> mg_chunk_off;
     // plo_records_index_dev: the entries and its two words (lowest offender << 4 | kind, n_placed)
     DevBuf bai_entry, bai_blk;
     HostBuf h_bai;
@@ -2337,6 +2371,8 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
                       &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk, &c->eqx_len, &c->eqx_off, &c->eqx_partial, &c->eqx_ops, &c->eqx_blk,
                       &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk,
+                      &c->mg_key[0], &c->mg_key[1], &c->mg_src[0], &c->mg_src[1], &c->mg_runof, &c->mg_len, &c->mg_mlen, &c->mg_off, &c->mg_partial, &c->mg_runs, &c->mg_first, &c->mg_blk, &c->mg_cfirst,
+                      &c->mg_coff, &c->mg_out, &c->mg_ooff,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
                       &c->counters, &c->big_list, &c->huge_list, &c->verr, &c->scratch, &c->tile_lo, &c->d_n_m, &c->d_in_off, &c->d_n_in, &c->d_pos1,
                       &c->d_w0, &c->d_w1, &c->d_kv0, &c->d_kv1, &c->d_flags, &c->d_contig, &c->d_seq_len, &c->d_seq_off, &c->d_shift_ref,
@@ -2346,7 +2382,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai, &c->h_mg, &c->h_mg_tab};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2372,6 +2408,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->xev[i]) (void)hipEventDestroy(c->xev[i]);
+    for (int i = 0; i < 4; ++i)
+        if (c->gev[i]) (void)hipEventDestroy(c->gev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
     if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -4088,6 +4126,217 @@ plo_status plo_records_sort_dev(plo_ctx *c, const plo_sort_in *in, plo_sort_out 
     out->perm = perm;
     out->key = (const uint64_t *)d.key[cur];
     out->n_mapped = h[1];
+    return PLO_OK;
+}
+
+// The merged order of in->runs (merge_core.hpp): k_merge_keys, a k_merge_rank per doubling of the groups of runs, k_merge_gather, the 64-bit
+// scan of the lengths, k_merge_chunks.  6 + ceil(log2(n_runs)) launches, one wait: the chunk table comes down with the result words.
+plo_status plo_runs_merge_plan_dev(plo_ctx *c, const plo_merge_in *in, plo_merge_out *out) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_run = out->err_record = UINT32_MAX;
+    c->err.clear();
+    c->have_plan = false;
+    static_assert(sizeof(plo_merge_run) == sizeof(MergeRun) && offsetof(plo_merge_run, record_off) == offsetof(MergeRun, record_off), "plo_merge_run and MergeRun are one layout");
+    static_assert(PLO_MERGE_MAX_RUNS == MERGE_MAX_RUNS && MERGE_MAX_RUNS <= 65536, "run_of holds a run in 16 bits");
+    if (in->n_runs > PLO_MERGE_MAX_RUNS || in->chunk_bytes == 0 || (in->n_runs && !in->runs) || in->n_ref > 0x7fffffffu) {
+        c->err = "plo_merge_in: at most " + std::to_string(PLO_MERGE_MAX_RUNS) + " runs, a chunk_bytes above 0, the run table and at most 2^31 - 1 references are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const uint32_t n_runs = in->n_runs;
+    uint64_t n64 = 0, n_bytes = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const plo_merge_run &run = in->runs[r];
+        if (run.n_records ? (!run.bytes || !run.record_off) : run.n_bytes != 0) {
+            c->err = "plo_merge_in: run " + std::to_string(r) + (run.n_records ? ": the records and their offsets are required" : ": bytes without a record");
+            return PLO_ERR_INVALID_ARG;
+        }
+        n64 += run.n_records;
+        n_bytes += run.n_bytes;
+    }
+    if (n64 > 0xfffffffeull) {
+        c->err = "plo_runs_merge_plan_dev: more than 2^32 - 2 records in all";
+        return PLO_ERR_RANGE;
+    }
+    const uint32_t n = (uint32_t)n64;
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!c->gev[i]) HIP_TRY(c, hipEventCreate(&c->gev[i]));
+    HIP_TRY(c, c->mg_off.ensure(((size_t)n + 1) * 8));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(c, c->mg_key[i].ensure((size_t)std::max(1u, n) * 8));
+        HIP_TRY(c, c->mg_src[i].ensure((size_t)std::max(1u, n) * 4));
+    }
+    c->mg_chunk_first.assign(1, 0);
+    c->mg_chunk_off.assign(1, 0);
+    c->mg_n = n;
+    c->mg_n_chunks = 0;
+    c->mg_cur = 0;
+    out->src = c->mg_src[0].as<uint32_t>();
+    out->key = c->mg_key[0].as<uint64_t>();
+    out->record_off = c->mg_off.as<uint64_t>();
+    out->chunk_first = c->mg_chunk_first.data();
+    out->chunk_off = c->mg_chunk_off.data();
+    if (!n) {
+        HIP_TRY(c, hipMemsetAsync(c->mg_off.p, 0, 8, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        c->have_plan = true;
+        return PLO_OK;
+    }
+    // two chunks in a row hold more than chunk_bytes (the second one's first record did not fit the first), and none is empty
+    const uint64_t cap64 = std::min<uint64_t>(n, 2 * (n_bytes / in->chunk_bytes) + 2);
+    const uint32_t cap = (uint32_t)cap64;
+    const uint32_t nb = (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK, nt = (uint32_t)(((uint64_t)n + 255u) / 256u);
+    const size_t tab_bytes = ((size_t)n_runs + 1) * 4, tab_at = (size_t)n_runs * sizeof(MergeRun);
+    HIP_TRY(c, c->mg_len.ensure((size_t)n * 8));
+    HIP_TRY(c, c->mg_mlen.ensure((size_t)n * 8));
+    HIP_TRY(c, c->mg_runof.ensure((size_t)n * 2));
+    HIP_TRY(c, c->mg_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->mg_runs.ensure(tab_at));
+    HIP_TRY(c, c->mg_first.ensure(tab_bytes));
+    HIP_TRY(c, c->mg_blk.ensure(16));
+    HIP_TRY(c, c->mg_cfirst.ensure(((size_t)cap + 1) * 4));
+    HIP_TRY(c, c->mg_coff.ensure(((size_t)cap + 1) * 8));
+    HIP_TRY(c, c->h_mg.ensure(tab_at + tab_bytes + 64));
+    HIP_TRY(c, c->h_mg_tab.ensure(((size_t)cap + 1) * 12 + 16));
+    uint8_t *hp = c->h_mg.as<uint8_t>();
+    memcpy(hp, in->runs, tab_at);
+    uint32_t *h_first = (uint32_t *)(hp + tab_at);
+    h_first[0] = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) h_first[r + 1] = h_first[r] + in->runs[r].n_records;
+    uint32_t *h = (uint32_t *)(hp + ((tab_at + tab_bytes + 15) & ~(size_t)15));
+    h[0] = (uint32_t)merge_err_word(MERGE_NO_RECORD);
+    h[1] = h[2] = h[3] = 0;
+    h[4] = h[5] = 0;
+    DevMerge d;
+    memset(&d, 0, sizeof(d));
+    d.runs = c->mg_runs.as<MergeRun>();
+    d.run_first = c->mg_first.as<uint32_t>();
+    d.n_runs = n_runs;
+    d.n = n;
+    d.n_ref = in->n_ref;
+    d.chunk_bytes = in->chunk_bytes;
+    for (int i = 0; i < 2; ++i) {
+        d.key[i] = c->mg_key[i].as<unsigned long long>();
+        d.src[i] = c->mg_src[i].as<uint32_t>();
+    }
+    d.run_of = c->mg_runof.as<uint16_t>();
+    d.len = c->mg_len.as<unsigned long long>();
+    d.mlen = c->mg_mlen.as<unsigned long long>();
+    unsigned long long *off = c->mg_off.as<unsigned long long>();
+    d.off = off;
+    d.err = c->mg_blk.as<int>();
+    d.res = c->mg_blk.as<uint32_t>() + 1;
+    d.chunk_first = c->mg_cfirst.as<uint32_t>();
+    d.chunk_off = c->mg_coff.as<unsigned long long>();
+    d.chunk_cap = cap;
+    HIP_TRY(c, hipMemcpyAsync(c->mg_runs.p, hp, tab_at, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->mg_first.p, h_first, tab_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->mg_blk.p, h, 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->gev[0], st));
+    hipLaunchKernelGGL(k_merge_keys, dim3(nt), dim3(256), 0, st, d);
+    int cur = 0;
+    for (uint32_t t = 0; (1u << t) < n_runs; ++t, cur ^= 1)
+        hipLaunchKernelGGL(k_merge_rank, dim3(nt), dim3(256), 0, st, d, (const unsigned long long *)d.key[cur], (const uint32_t *)d.src[cur], d.key[cur ^ 1], d.src[cur ^ 1], t);
+    hipLaunchKernelGGL(k_merge_gather, dim3(nt), dim3(256), 0, st, d, (const uint32_t *)d.src[cur]);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.mlen, n, nb, c->mg_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->mg_partial.as<unsigned long long>(), n, nb, off);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.mlen, n, nb, (const unsigned long long *)c->mg_partial.as<unsigned long long>(), off);
+    hipLaunchKernelGGL(k_merge_chunks, dim3(1), dim3(64), 0, st, d, (const unsigned long long *)d.key[cur]);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->gev[1], st));
+    uint8_t *ht = c->h_mg_tab.as<uint8_t>();
+    HIP_TRY(c, hipMemcpyAsync(h, c->mg_blk.p, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(ht, c->mg_coff.p, ((size_t)cap + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(ht + ((size_t)cap + 1) * 8, c->mg_cfirst.p, ((size_t)cap + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)merge_err_word(MERGE_NO_RECORD)) {
+        const uint32_t g = h[0] ^ 0x80000000u;
+        HIP_TRY(c, hipMemcpy(h + 4, d.len + g, 8, hipMemcpyDeviceToHost));
+        uint32_t r = 0;
+        while (r + 1 < n_runs && h_first[r + 1] <= g) ++r;
+        static const char *const what[] = {"", "record_off: it must start at 0, not decrease and end at the run's n_bytes", "its length: fewer than the 36 bytes of block_size and the fixed fields",
+                                           "block_size: block_size + 4 differs from the record's length", "refID: outside [-1, n_ref)", "pos: outside [-1, 2^31 - 2]",
+                                           "its place: its key is lower than the key of the record before it, the run is not coordinate sorted"};
+        out->err_run = r;
+        out->err_record = g - h_first[r];
+        out->err_kind = h[4];
+        out->src = nullptr;
+        out->key = nullptr;
+        out->record_off = nullptr;
+        out->chunk_first = nullptr;
+        out->chunk_off = nullptr;
+        c->err = "plo_runs_merge_plan_dev: run " + std::to_string(r) + " record " + std::to_string(out->err_record) + " is refused for kind " + std::to_string(h[4]) + ", " +
+                 (h[4] >= 1 && h[4] <= 6 ? what[h[4]] : "an unknown reason") + "; nothing was merged";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const uint32_t n_chunks = h[2];
+    if (n_chunks == 0 || n_chunks > cap) {
+        c->err = "plo_runs_merge_plan_dev: the chunk table outgrew its bound";
+        return PLO_ERR_INTERNAL;
+    }
+    const uint64_t *t_off = (const uint64_t *)ht;
+    const uint32_t *t_first = (const uint32_t *)(ht + ((size_t)cap + 1) * 8);
+    c->mg_chunk_first.assign(t_first, t_first + n_chunks + 1);
+    c->mg_chunk_off.assign(t_off, t_off + n_chunks + 1);
+    (void)hipEventElapsedTime(&out->plan_ms, c->gev[0], c->gev[1]);
+    c->mg_cur = cur;
+    c->mg_n_chunks = n_chunks;
+    c->have_plan = true;
+    out->n_records = n;
+    out->n_mapped = h[1];
+    out->n_bytes = c->mg_chunk_off[n_chunks];
+    out->src = d.src[cur];
+    out->key = (const uint64_t *)d.key[cur];
+    out->n_chunks = n_chunks;
+    out->chunk_first = c->mg_chunk_first.data();
+    out->chunk_off = c->mg_chunk_off.data();
+    return PLO_OK;
+}
+
+// Chunk `chunk` of the context's current plan (merge_core.hpp): ONE launch of k_merge_copy, a wave per 16 KB of the chunk, one wait.
+plo_status plo_runs_merge_emit_dev(plo_ctx *c, uint32_t chunk, plo_merge_chunk_out *out) {
+    if (!c || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    c->err.clear();
+    if (!c->have_plan) {
+        c->err = "plo_runs_merge_emit_dev: the context holds no plan (plo_runs_merge_plan_dev first; a refused plan is none)";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (chunk >= c->mg_n_chunks) {
+        c->err = "plo_runs_merge_emit_dev: chunk " + std::to_string(chunk) + " of a plan of " + std::to_string(c->mg_n_chunks);
+        return PLO_ERR_INVALID_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    hipStream_t st = c->stream;
+    const uint32_t first = c->mg_chunk_first[chunk], nrec = c->mg_chunk_first[chunk + 1] - first;
+    const uint64_t nbytes = c->mg_chunk_off[chunk + 1] - c->mg_chunk_off[chunk];
+    HIP_TRY(c, c->mg_out.ensure((size_t)nbytes + 16));
+    HIP_TRY(c, c->mg_ooff.ensure(((size_t)nrec + 1) * 8));
+    DevMergeEmit d;
+    memset(&d, 0, sizeof(d));
+    d.runs = c->mg_runs.as<MergeRun>();
+    d.run_first = c->mg_first.as<uint32_t>();
+    d.run_of = c->mg_runof.as<uint16_t>();
+    d.src = c->mg_src[c->mg_cur].as<uint32_t>();
+    d.off = c->mg_off.as<unsigned long long>();
+    d.first = first;
+    d.n = nrec;
+    d.out = c->mg_out.as<uint8_t>();
+    d.out_off = c->mg_ooff.as<unsigned long long>();
+    const unsigned long long n_pieces = (nbytes + MERGE_COPY_PIECE - 1) / MERGE_COPY_PIECE;
+    HIP_TRY(c, hipEventRecord(c->gev[2], st));
+    hipLaunchKernelGGL(k_merge_copy, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, st, d, n_pieces);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->gev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->emit_ms, c->gev[2], c->gev[3]);
+    out->bytes = d.out;
+    out->n_bytes = nbytes;
+    out->n_records = nrec;
+    out->first_record = first;
+    out->record_off = (const uint64_t *)d.out_off;
     return PLO_OK;
 }
 

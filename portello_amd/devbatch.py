@@ -529,3 +529,55 @@ class DeviceBlocks:
         if self._pool is not None and self._block is not None:
             self._pool.give(self._block)
         self._block = None
+
+
+class RetainedWindow:
+    """one window's coordinate-sorted records kept on the device in allocations of its own: a device-to-device copy of the plo_sort_out
+    of api.Engine.records_sort_dev, which the context overwrites at its next sort.  What api.Engine.runs_merge_plan_dev takes as a run
+    (`run()`); the copy is made on the current stream and waited for, so another thread's context may read it.  `free()` gives the
+    memory back."""
+
+    def __init__(self, so: abi.PloSortOut, dev=None):
+        from .gather import device_view
+
+        self.n_bytes, self.n_records = int(so.n_bytes), int(so.n_records)
+        self.raw = torch.empty(max(16, self.n_bytes), dtype=torch.uint8, device=dev)
+        self.off = torch.empty((self.n_records + 1) * 8, dtype=torch.uint8, device=dev)
+        if self.n_bytes:
+            self.raw[:self.n_bytes].copy_(device_view(so.bytes, self.n_bytes, torch.uint8, dev), non_blocking=True)
+        self.off.copy_(device_view(so.record_off, (self.n_records + 1) * 8, torch.uint8, dev), non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+
+    def run(self):
+        """(bytes, n_bytes, n_records, record_off) as device addresses"""
+        return self.raw.data_ptr(), self.n_bytes, self.n_records, self.off.data_ptr()
+
+    def free(self):
+        self.raw = self.off = None
+
+
+class MergedChunk:
+    """a chunk of a merge plan (api.Engine.runs_merge_emit_dev) in the shape DeviceRecords and DeviceBlocks take for `ro`: bytes, n_bytes,
+    n_records, record_off; the counts of the lift are the windows' own and stay with them (0 here).  Good until the engine's next emit."""
+    n_lifted = n_unmapped_copies = 0
+    records_ms = 0.0
+
+    def __init__(self, co: abi.PloMergeChunkOut, chunk: int):
+        self.chunk, self.bytes, self.n_bytes, self.n_records, self.record_off = chunk, co.bytes, int(co.n_bytes), int(co.n_records), co.record_off
+        self.first_record, self.emit_ms = int(co.first_record), float(co.emit_ms)
+
+
+def merged_chunks(eng, plan: abi.PloMergeOut):
+    """the chunks of `plan` (api.Engine.runs_merge_plan_dev on `eng`), emitted one after the other in merged order: every MergedChunk is good
+    until the next one is asked for, so the consumer indexes, compresses or downloads it before it goes on"""
+    for c in range(int(plan.n_chunks)):
+        yield MergedChunk(eng.runs_merge_emit_dev(c), c)
+
+
+class RetainedCounts:
+    """what the pipeline counts of a window whose records stay on the device for the merger: the fields of DeviceRecords without a byte"""
+    bytes = None
+
+    def __init__(self, ro: abi.PloRecordsOut):
+        self.n_bytes, self.n_records = int(ro.n_bytes), int(ro.n_records)
+        self.n_lifted, self.n_unmapped_copies, self.records_ms = int(ro.n_lifted), int(ro.n_unmapped_copies), float(ro.records_ms)

@@ -75,6 +75,9 @@ class PipelineStats:
     eqx_device_ms: float = 0.0  # emit_eqx: HIP-event time of plo_eqx_dev (= / X CIGARs of the lifted records: count, scan, emit)
     index_device_ms: float = 0.0  # index_runs: HIP-event time of plo_records_index_dev (a wave per record of the sorted buffer)
     index_paths: List[str] = field(default_factory=list)  # index_runs: <run>.bai of every run of out_paths, in the same order
+    merge_plan_device_ms: float = 0.0  # run_windows != 1: HIP-event time of plo_runs_merge_plan_dev (check + keys, rank rounds, offsets, chunk table)
+    merge_emit_device_ms: float = 0.0  # run_windows != 1: HIP-event time of plo_runs_merge_emit_dev, summed over the chunks
+    run_groups: List[int] = field(default_factory=list)  # sorted_runs: the windows with records in every written run, in out_paths order (all 1 with run_windows=1)
     sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
@@ -91,8 +94,26 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    write_threads: Optional[int] = None, ramp: bool = True, part: Optional[int] = None, n_parts: int = 1,
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
                    device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False,
-                   index_runs: bool = False, emit_eqx: bool = False) -> PipelineStats:  # noqa: E501
-    """emit_eqx (default off; needs device_records=True): every lifted record leaves with a pbmm2-style CIGAR, every M op replaced by its
+                   index_runs: bool = False, emit_eqx: bool = False, run_windows: int = 1, run_budget_bytes: Optional[int] = None,
+                   run_chunk_bytes: int = 1 << 30) -> PipelineStats:  # noqa: E501
+    """run_windows (default 1; anything else needs sorted_runs=True): how many windows leave as one run.  1: every window is a run of its
+    own, as below -- same file names, same bytes, no new allocation.  K > 1: the windows [mK, (m + 1)K) of a reader, by the reader's window
+    sequence number and not by arrival at the lift workers, form group m.  Every worker keeps its sorted window on the device
+    (devbatch.RetainedWindow: a device-to-device copy of plo_sort_out) and hands it to ONE merger thread with a context of its own on the
+    same device; the merger plans the group's merge (plo_runs_merge_plan_dev: the order of plo_records_sort_dev over the windows'
+    concatenation, which is the order of bam.merge_runs over the windows' runs), and for every chunk of at most run_chunk_bytes it emits
+    (plo_runs_merge_emit_dev), indexes with index_runs, compresses on the device with device_bgzf or else downloads for the host writer,
+    and writes ONE run <stem>.r<reader:02d>m<group:06d><ext> (plus .bai), then frees the group.  0: all windows of a reader are one
+    group; with n_readers == 1 and one group that single run is written to `out_path` itself (and out_path + ".bai"): a sorted, indexed BAM
+    with nothing left to merge.  run_budget_bytes: a reader's group is closed early, in window order, when the next window would take
+    its retained bytes past the reader's share of the budget (run_budget_bytes // n_readers), so a group's composition is a function of
+    the windows' sizes alone; a worker waits while the groups that are being written hold the reader's share, and a window larger than
+    it forms a group alone.  Default: half of the device's free memory when the pipeline starts -- a policy, not a measurement: the
+    workers' own buffers, the merger's chunk and the allocator's cache take their share of the other half.  Groups closed early are
+    numbered on (m counts the groups of the reader).  A window without an output record takes its place in its group and is not
+    counted.  PipelineStats: merge_plan_device_ms, merge_emit_device_ms, run_groups (the windows with records of every written run), out_paths / index_paths in name order, which stays the tie order of bam.merge_runs.  Combines with
+    emit_nm, emit_md, emit_eqx, device_bgzf, index_runs, device_batch and device_input.
+    emit_eqx (default off; needs device_records=True): every lifted record leaves with a pbmm2-style CIGAR, every M op replaced by its
     maximal runs of '=' (the read's base matches the reference chromosome of the index, by emit_nm's pair rule) and 'X' (it does not);
     every other op stays (plo_eqx_dev between the finishing and plo_records_build_dev, which then writes these ops, by bam_write1's rule
     in CG:B,I where there are more than 65535 of them).  Positions, bins, reference ends and SA:Z, whose CIGARs stay in M, do not
@@ -165,6 +186,15 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # threads inside the stages (inflate / batch construction, record assembly per worker, BGZF output).  The stages run at the same
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
+    run_windows = int(run_windows)
+    if run_windows != 1 and not sorted_runs:
+        raise ValueError("run_windows merges the coordinate-sorted windows of a group into one run: it needs sorted_runs=True")
+    if run_windows < 0:
+        raise ValueError("run_windows is 0 (all windows of a reader), 1 (a run per window) or the number of windows of a run")
+    if run_windows != 1 and int(run_chunk_bytes) <= 0:
+        raise ValueError("run_chunk_bytes is the size of the chunks a merged run is emitted in: it must be above 0")
+    if run_windows != 1 and run_budget_bytes is not None and int(run_budget_bytes) <= 0:
+        raise ValueError("run_budget_bytes is the device memory the retained windows may hold: it must be above 0 (None: half of the free memory)")
     if index_runs and not sorted_runs:
         raise ValueError("index_runs writes the BAM index of every coordinate-sorted run: it needs sorted_runs=True")
     if sorted_runs and not device_records:
@@ -244,6 +274,109 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
             except queue.Empty:
                 pass
         return None
+
+    merge_windows = sorted_runs and run_windows != 1
+    if merge_windows:
+        import torch as _torch
+
+        if run_budget_bytes is None:
+            run_budget_bytes = _torch.cuda.mem_get_info(index.device)[0] // 2
+        share = max(1, int(run_budget_bytes) // len(rds))  # a reader's part of the budget: no reader waits for another one's open group
+        q_merge: "queue.Queue" = queue.Queue()
+        mcond = threading.Condition()
+        # per reader: the next window to take its place, the open group (windows, their retained bytes), the bytes of the groups on their
+        # way through the merger, the groups closed so far
+        m_next, m_open, m_open_bytes, m_closing, m_groups = [0] * len(rds), [[] for _ in rds], [0] * len(rds), [0] * len(rds), [0] * len(rds)
+        written = []  # (path, windows of the run)
+
+    def close_group(ci):  # (under mcond)
+        if m_open[ci]:
+            q_merge.put((ci, m_groups[ci], m_open[ci], m_open_bytes[ci]))
+            m_closing[ci] += m_open_bytes[ci]
+            m_groups[ci] += 1
+            m_open[ci], m_open_bytes[ci] = [], 0
+
+    def retain(run_id, n_bytes, make):
+        """the window takes its place in its reader's open group, in window order: make() -> the devbatch.RetainedWindow (None: no record)"""
+        ci, seq = run_id
+        with mcond:
+            while m_next[ci] != seq and not abort.is_set():
+                mcond.wait(0.2)
+            if m_open[ci] and ((run_windows and len(m_open[ci]) >= run_windows) or m_open_bytes[ci] + n_bytes > share):
+                close_group(ci)
+            while m_closing[ci] and m_closing[ci] + m_open_bytes[ci] + n_bytes > share and not abort.is_set():
+                mcond.wait(0.2)
+        held = make() if not abort.is_set() else None
+        with mcond:
+            m_open[ci].append(held)
+            m_open_bytes[ci] += n_bytes
+            m_next[ci] = seq + 1
+            mcond.notify_all()
+
+    def merger():
+        eng = None
+        try:
+            import torch
+
+            from . import devbatch
+            dev = torch.device("cuda", index.device)
+            tstream = torch.cuda.Stream(device=dev)
+            eng = api.Engine(index, stream=tstream.cuda_stream)
+            pool = devbatch.PinnedPool()
+            while True:
+                item = get(q_merge)
+                if item is None:
+                    break
+                ci, group, held, nbytes = item
+                runs = [h for h in held if h is not None and h.n_records]
+                if runs:
+                    if run_windows == 0 and len(rds) == 1 and group == 0:
+                        run_path = out_path + ".m000000"  # renamed to out_path when it stays the only one
+                    else:
+                        run_path = "%s.r%02dm%06d%s" % (run_stem, ci, group, run_ext)
+                    with torch.cuda.stream(tstream):
+                        plan = eng.runs_merge_plan_dev([h.run() for h in runs], len(ref_names), int(run_chunk_bytes))
+                        wr = bam.BamWriter(run_path, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads),
+                                           index_path=run_path + ".bai" if index_runs else None)
+                        emit_ms = index_ms = bgzf_ms = 0.0
+                        for ch in devbatch.merged_chunks(eng, plan):
+                            ixo = None
+                            if index_runs:
+                                ixo = eng.records_index_dev(ch.bytes, ch.n_bytes, ch.n_records, ch.record_off, len(ref_names))
+                                index_ms += float(ixo.index_ms)
+                            if device_bgzf:
+                                rb = devbatch.DeviceBlocks(eng, ch, 0 if level == 0 else 1, pool=pool, dev=dev, index_out=ixo)
+                                bgzf_ms += rb.bgzf_ms
+                            else:
+                                rb = devbatch.DeviceRecords(ch, pool=pool, dev=dev, index_out=ixo)
+                            if index_runs:
+                                wr.index_add(rb.index_entries)
+                            if device_bgzf:
+                                wr.write_blocks((rb.bytes, rb.n_bytes))
+                            else:
+                                wr.write((rb.bytes, rb.n_bytes))
+                            rb.release()
+                            emit_ms += ch.emit_ms
+                        wr.close()
+                    with lock:
+                        written.append((run_path, len(runs)))
+                        st.merge_plan_device_ms += float(plan.plan_ms)
+                        st.merge_emit_device_ms += emit_ms
+                        st.index_device_ms += index_ms
+                        st.bgzf_device_ms += bgzf_ms
+                for h in held:
+                    if h is not None:
+                        h.free()
+                with mcond:
+                    m_closing[ci] -= nbytes
+                    mcond.notify_all()
+        except BaseException as e:  # noqa: BLE001
+            st.errors.append(f"merger: {e!r}")
+            abort.set()
+        finally:
+            st.stage_done_s["merger"] = time.perf_counter() - t0
+            if eng is not None:
+                eng.close()
 
     # the input side is two stages: BGZF inflate + record walk (read_window), then the window's batch arrays (batch_desc: CIGARs,
     # bases, qualities gathered into the plo_batch_in layout) -- about half of the reader's time each
@@ -381,18 +514,23 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 sort_ms = float(srt.sort_ms)
                                 marks.append(("sort", time.perf_counter()))
                             ixo, index_ms = None, 0.0
-                            if index_runs and srt is not None:
+                            if merge_windows:  # the sorted window stays on the device; the merger writes its group's run
+                                rb = devbatch.RetainedCounts(ro)
+                                retain(run_id, int(ro.n_bytes), (lambda: devbatch.RetainedWindow(srt, dev)) if srt is not None else (lambda: None))
+                                marks.append(("retain", time.perf_counter()))
+                            elif index_runs and srt is not None:
                                 ixo = eng.records_index_dev(srt.bytes, srt.n_bytes, srt.n_records, srt.record_off, len(ref_names))
                                 index_ms = float(ixo.index_ms)
                                 marks.append(("index", time.perf_counter()))
-                            if device_bgzf:
+                            if not merge_windows and device_bgzf:
                                 rb = devbatch.DeviceBlocks(eng, ro, 0 if level == 0 else 1, pool=pool, dev=dev, sorted_out=srt, index_out=ixo)
                                 marks.append(("bgzf", time.perf_counter() - rb.block_s - rb.copy_s))
-                            else:
+                            elif not merge_windows:
                                 rb = devbatch.DeviceRecords(ro, pool=pool, dev=dev, sorted_out=srt, index_out=ixo)
-                            now = time.perf_counter()
-                            marks.append(("download: page-locked block", now - rb.copy_s))
-                            marks.append(("download: copy", now))
+                            if not merge_windows:
+                                now = time.perf_counter()
+                                marks.append(("download: page-locked block", now - rb.copy_s))
+                                marks.append(("download: copy", now))
                         t1 = time.perf_counter()
                         with lock:
                             for (_, a), (name, b) in zip(marks, marks[1:]):
@@ -449,6 +587,8 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                         st.lifted += int(rb.n_lifted)
                         st.unmapped_copies += int(rb.n_unmapped_copies)
                         st.bytes_out += int(getattr(rb, "n_in", rb.n_bytes))
+                elif merge_windows:
+                    retain(run_id, 0, lambda: None)  # a window without a primary record still takes its place in its group
                 put(q_out, (win, rb, run_id))
         except BaseException as e:  # noqa: BLE001
             st.errors.append(f"lift worker {k}: {e!r}")
@@ -481,7 +621,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                     break
                 win, rb, run_id = item
                 t = time.perf_counter()
-                if rb is not None and rb.n_bytes:
+                if rb is not None and rb.n_bytes and not merge_windows:
                     if sorted_runs:  # the window's run: a complete BAM of its own
                         run_path = "%s.r%02dw%06d%s" % (run_stem, run_id[0], run_id[1], run_ext)
                         wr = bam.BamWriter(run_path, hdr_out, ref_names, ref_lens, level=level, n_threads=max(1, write_threads),
@@ -519,8 +659,32 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     writers = [threading.Thread(target=writer, args=(k,)) for k in range(out_shards)]
     for t in front + writers:
         t.start()
+    if merge_windows:
+        t_merger = threading.Thread(target=merger)
+        t_merger.start()
     for t in front:
         t.join()
+    if merge_windows:
+        with mcond:
+            for ci in range(len(rds)):
+                close_group(ci)
+        q_merge.put(None)
+        t_merger.join()
+        written.sort()
+        if run_windows == 0 and len(rds) == 1 and written and not st.errors:
+            if len(written) == 1:  # the run is the output
+                os.replace(written[0][0], out_path)
+                if index_runs:
+                    os.replace(written[0][0] + ".bai", out_path + ".bai")
+                written = [(out_path, written[0][1])]
+            else:  # the budget cut the reader's windows into several groups: the first one takes its name among them
+                first = "%s.r%02dm%06d%s" % (run_stem, 0, 0, run_ext)
+                os.replace(written[0][0], first)
+                if index_runs:
+                    os.replace(written[0][0] + ".bai", first + ".bai")
+                written[0] = (first, written[0][1])
+                written.sort()
+        out_paths.extend(p_ for p_, _ in written)
     for _ in writers:
         put(q_out, None)
     for t in writers:
@@ -529,10 +693,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         wr.close()
     if sorted_runs:
         if not out_paths and not st.errors:  # no output record at all: one header-only run, so that a merge has a header
-            out_paths.append("%s.r%02dw%06d%s" % (run_stem, 0, 0, run_ext))
+            out_paths.append(out_path if run_windows == 0 and len(rds) == 1 else "%s.r%02d%s%06d%s" % (run_stem, 0, "m" if merge_windows else "w", 0, run_ext))
             bam.BamWriter(out_paths[0], hdr_out, ref_names, ref_lens, level=level, n_threads=1, index_path=out_paths[0] + ".bai" if index_runs else None).close()
         out_paths.sort()
         st.out_paths = list(out_paths)
+        st.run_groups = [dict(written).get(p_, 0) for p_ in out_paths] if merge_windows else [1] * len(out_paths)
         if index_runs:
             st.index_paths = [p_ + ".bai" for p_ in out_paths]
     st.out_file_bytes = sum(os.path.getsize(p_) for p_ in out_paths if os.path.exists(p_))

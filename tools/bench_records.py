@@ -26,6 +26,9 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_records_sort_dev on the window's records (--sort-out; this leg runs alone): sort_ms beside the window's records_ms, and one
     device-to-device hipMemcpyAsync of n_bytes taken in the same process (the floor of the permuted copy).  perm, key, record_off and the
     bytes are compared with the order computed on the host (numpy, from the definition of the key) before anything is timed
+  - plo_runs_merge_plan_dev / plo_runs_merge_emit_dev on --merge-windows sorted, retained windows (--merge-out; this leg runs alone): plan_ms
+    and the summed emit_ms beside plo_records_sort_dev over the windows' concatenation and a device-to-device copy of the same bytes;
+    the merged bytes are compared with that sort's output before any timing
   - plo_records_index_dev on the window's sorted records (--index-out; this leg runs alone): index_ms beside the window's sort_ms and
     records_ms, and one device-to-device hipMemcpyAsync of the call's algorithmic read bytes (36 + 4 n_cigar_op a record) taken in the
     same process; the entries are compared with those computed on the host (numpy, from the rule) before anything is timed.  On the CPU:
@@ -45,6 +48,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --nm-out profiles/r13_nm_window.json --md-out profiles/r13_md_window.json
     python tools/bench_records.py --reads 50000 --sort-out profiles/r14_sort_window.json
     python tools/bench_records.py --reads 50000 --index-out profiles/r15_index_window.json
+    python tools/bench_records.py --reads 50000 --merge-out profiles/r18_merge_runs.json --merge-windows 4
 """
 import argparse
 import ctypes as C
@@ -694,6 +698,104 @@ def sort_leg(a, win, index, cn, rn, dev):
     return res, bool(same)
 
 
+def merge_leg(a, rd, index, cn, rn, dev):
+    """K windows: each is lifted, its records are sorted (plo_records_sort_dev) and retained on the device (devbatch.RetainedWindow); then
+    plo_runs_merge_plan_dev and the plo_runs_merge_emit_dev calls of all chunks, against plo_records_sort_dev over the concatenation of the K
+    retained windows -- the way to get the same buffer without the merge -- and a device-to-device copy of the same bytes"""
+    import numpy as np
+    import torch
+
+    from portello_amd import api, build, devbatch
+    from portello_amd.gather import device_view
+
+    eng = api.Engine(index)
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    n_ref, K = len(rn), max(1, a.merge_windows)
+    per, held, sort_window_ms = (a.reads + K - 1) // K, [], []
+    for k in range(K):
+        win = rd.read_window(per)
+        if win is None or not win.n_records:
+            break
+        b, f, r = win.batch_raw()
+        up = devbatch.upload_raw_window(b, f, r, dev)
+        torch.cuda.synchronize()
+        ddesc = up.batch.desc()
+        out = eng.liftover_batch_dev(ddesc)
+        eng.compact_output_dev(out)
+        eng.finish_batch_dev(ddesc, up.finish_in())
+        eng.sa_segments_dev(sa_in)
+        ro = eng.records_build_dev(ddesc, up.records_in(labels, False))
+        so = eng.records_sort_dev(ro.bytes, int(ro.n_bytes), int(ro.n_records), ro.record_off, n_ref)
+        sort_window_ms.append(float(so.sort_ms))
+        held.append(devbatch.RetainedWindow(so, dev))
+        del up
+        win.close()
+    n, nb = sum(h.n_records for h in held), sum(h.n_bytes for h in held)
+    runs = [h.run() for h in held]
+    # the concatenation of the retained windows: the input of the sort the merge is read against
+    cat = torch.empty(max(16, nb), dtype=torch.uint8, device=dev)
+    cat_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    at_b = at_r = 0
+    for h in held:
+        cat[at_b:at_b + h.n_bytes].copy_(h.raw[:h.n_bytes])
+        cat_off[at_r:at_r + h.n_records + 1].copy_(h.off.view(torch.int64) + at_b)
+        at_b, at_r = at_b + h.n_bytes, at_r + h.n_records
+    torch.cuda.synchronize()
+
+    def down(ptr, count, dtype):
+        return device_view(ptr, count * np.dtype(dtype).itemsize, torch.uint8, dev).cpu().numpy().view(dtype) if count else np.zeros(0, dtype)
+
+    # the merged bytes against that sort's output, before any timing
+    so = eng.records_sort_dev(cat.data_ptr(), nb, n, cat_off.data_ptr(), n_ref)
+    want, want_off = down(so.bytes, nb, np.uint8).copy(), down(so.record_off, n + 1, np.uint64).copy()
+    po = eng.runs_merge_plan_dev(runs, n_ref, a.merge_chunk_bytes)
+    nc = int(po.n_chunks)
+    same = (int(po.n_records) == n and int(po.n_bytes) == nb and int(po.n_mapped) == int(so.n_mapped) and np.array_equal(down(po.src, n, np.uint32), down(so.perm, n, np.uint32)) and
+            np.array_equal(down(po.key, n, np.uint64), down(so.key, n, np.uint64)) and np.array_equal(down(po.record_off, n + 1, np.uint64), want_off))
+    chunk_off = np.ctypeslib.as_array(po.chunk_off, (nc + 1,)).copy()
+    chunk_records = np.diff(np.ctypeslib.as_array(po.chunk_first, (nc + 1,))).tolist()
+    for c in range(nc):
+        co = eng.runs_merge_emit_dev(c)
+        same = same and np.array_equal(down(co.bytes, int(co.n_bytes), np.uint8), want[int(chunk_off[c]):int(chunk_off[c + 1])])
+    del want
+    plan_ms, emit_ms, plan_wall, emit_wall, sort_ms = [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        t0 = time.perf_counter()
+        po = eng.runs_merge_plan_dev(runs, n_ref, a.merge_chunk_bytes)
+        t1 = time.perf_counter()
+        e = sum(float(eng.runs_merge_emit_dev(c).emit_ms) for c in range(nc))
+        t2 = time.perf_counter()
+        so = eng.records_sort_dev(cat.data_ptr(), nb, n, cat_off.data_ptr(), n_ref)
+        if k >= a.warmup:
+            plan_ms.append(float(po.plan_ms))
+            emit_ms.append(e)
+            plan_wall.append((t1 - t0) * 1e3)
+            emit_wall.append((t2 - t1) * 1e3)
+            sort_ms.append(float(so.sort_ms))
+    dst, d2d = torch.empty(max(16, nb), dtype=torch.uint8, device=dev), []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(cat, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {"tool": "tools/bench_records.py", "reads": a.reads, "windows": len(held), "window_records": [h.n_records for h in held], "records": n, "n_bytes": nb, "n_ref": n_ref,
+           "chunk_bytes": a.merge_chunk_bytes, "n_chunks": nc, "chunk_records": chunk_records,
+           "commit": a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None, "source_hash": build.source_hash(),
+           "warmup": a.warmup, "reps": a.reps, "equals_sort_of_concatenation": bool(same), "plan_launches_per_call": 6 + max(0, (len(held) - 1).bit_length()),
+           "plan_ms": stats(plan_ms), "emit_ms_summed_over_chunks": stats(emit_ms), "plan_call_wall_ms": stats(plan_wall), "emit_calls_wall_ms": stats(emit_wall),
+           "sort_of_concatenation_ms": stats(sort_ms), "sort_of_each_window_ms": sort_window_ms, "d2d_copy_n_bytes_ms": stats(d2d),
+           "emit_gbs_read_plus_write": 2 * nb / med(emit_ms) / 1e6, "d2d_copy_gbs_read_plus_write": 2 * nb / med(d2d) / 1e6,
+           "plan_plus_emit_over_sort_of_concatenation_time": (med(plan_ms) + med(emit_ms)) / med(sort_ms), "emit_over_d2d_copy_time": med(emit_ms) / med(d2d),
+           "not_measured": ["genome-size groups (dozens of windows of 1.2 GB)", "short records", "n_runs in the hundreds"]}
+    return res, bool(same)
+
+
 def index_leg(a, win, index, cn, rn, rl, dev):
     """ONE window: plo_records_index_dev on the sorted records, against the entries computed on the host and a device-to-device copy of the
     call's algorithmic bytes; then, on the CPU, the writer's close with and without an index and the merge of the window's two halves with
@@ -847,6 +949,9 @@ def main():
     ap.add_argument("--eqx-out", default="", help="run the = / X leg (plo_eqx_dev beside the window's nm, md, lift, finish and records times, against a device-to-device copy) and write its JSON there; alone or behind --nm-out / --md-out")
     ap.add_argument("--sort-out", default="", help="run the sort leg (plo_records_sort_dev on the window's records, against the host's expected order and a device-to-device copy of n_bytes) alone and write its JSON there")
     ap.add_argument("--index-out", default="", help="run the index leg (plo_records_index_dev on the window's sorted records, against the host's entries and a device-to-device copy of its algorithmic bytes; the writer's and the merge's index on the CPU) alone and write its JSON there")
+    ap.add_argument("--merge-out", default="", help="run the merge leg (--merge-windows windows sorted and retained on the device; plo_runs_merge_plan_dev and the summed plo_runs_merge_emit_dev against plo_records_sort_dev over their concatenation and a device-to-device copy of the same bytes) alone and write its JSON there")
+    ap.add_argument("--merge-windows", type=int, default=4, help="windows of the merge leg: --reads is cut into that many")
+    ap.add_argument("--merge-chunk-bytes", type=int, default=1 << 30, help="chunk_bytes of the merge leg's plan")
     a = ap.parse_args()
     signal.alarm(a.limit)
 
@@ -864,6 +969,14 @@ def main():
     index = api.Index(w.index_data_device())
     cn, rn = meta["contig_names"], bamsynth.ref_names(w)
     rd = bam.BamReader(path, 8)
+    if a.merge_out:
+        mres, ok = merge_leg(a, rd, index, cn, rn, dev)
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.merge_out)), exist_ok=True)
+        with open(a.merge_out, "w") as fh:
+            fh.write(json.dumps(mres, indent=1) + "\n")
+        print(json.dumps(mres))
+        sys.exit(0 if ok else 1)
     win = rd.read_window(a.reads + 10)
     assert win.n_records == a.reads
     if a.part_out:
