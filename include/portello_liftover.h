@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 18 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file; 18: plo_runs_merge_plan_dev / plo_runs_merge_emit_dev (sorted windows merged into large runs on the device) */
+#define PLO_API_VERSION 19 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file; 18: plo_runs_merge_plan_dev / plo_runs_merge_emit_dev (sorted windows merged into large runs on the device); 19: plo_depth_* (the depth of the records: difference array, scan, windows, runs) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -588,6 +588,119 @@ typedef struct plo_index_out {
 } plo_index_out;
 
 plo_status plo_records_index_dev(plo_ctx *ctx, const plo_index_in *in, plo_index_out *out);
+
+/* ---- Depth of the records (device-resident, opt-in; API version 19) ---------------------------------------------------------
+ * How many records cover every reference base, taken from the records while they lie on the device (plo_records_out, plo_sort_out, a
+ * merged chunk: any buffer of records with offsets) -- what `samtools depth` or `mosdepth` compute by reading the written file back.
+ * The input need not be sorted.
+ * THE OBJECT.  A depth object holds ONE int32 array for a list of chromosomes (n_ref, ref_len[], the output header's @SQ order).
+ *   Chromosome r owns a slot of ref_len[r] + 1 entries; the last one takes the -1 of an interval that ends at the chromosome's end.
+ *   Slots start at multiples of 64 entries: slot_off[0] = 0, slot_off[r + 1] = slot_off[r] + (ref_len[r] + 1 rounded up to 64).  The
+ *   entries between the slots stay zero.  The array has slot_off[n_ref] entries: 4 x the sum of (ref_len + 1), rounded up per slot -- about
+ *   12.4 GB for a human genome of 3.1 Gb -- plus the sums of the scan, 4 bytes per PLO_DEPTH_TILE (1024) entries.  plo_depth_info_get reports
+ *   the bytes the object holds.
+ * THE RULE.  A record is COUNTED iff refID >= 0, pos >= 0 and (FLAG & exclude_flags) == 0.  exclude_flags defaults to 0x704, the mask of
+ * mosdepth and samtools depth: unmapped, secondary, QC-fail, duplicate.  Supplementary records count.
+ *   Its ops are the record's REAL CIGAR: the in-record ops, or the ops of the record's first CG field when that is a B,I array and the
+ *   in-record CIGAR is the placeholder <l_seq>S<n>N (what plo_batch_build_dev takes as a read's CIGAR).  A placeholder without such a
+ *   field is taken as it stands, as htslib takes it: its N covers nothing.
+ *   Walking the ops from pos: M, =, X cover their reference bases; D covers them iff count_deletions is set (set: mosdepth and
+ *   `samtools depth -J`; clear, the default: `samtools depth`); N covers nothing and consumes reference; I, S, H, P and the codes 9-15
+ *   consume nothing; ops of length 0 are ignored.  The depth at a base is the number of counted records that cover it.
+ * CHECKED for every record of an add, counted or not, on the device, before a byte of it is trusted and before anything is added;
+ * kinds in err_kind, a record reports the first kind it breaks in this order:
+ *   1 .. 5  what plo_records_sort_dev checks, in its order: record_off, the 36 bytes, block_size, refID in [-1, n_ref), pos
+ *   6       36 + l_read_name + 4 n_cigar_op > 4 + block_size: the in-record CIGAR leaves the record (the index call's rule)
+ *   7       a record in placeholder form whose aux fields would begin behind its end, with a malformed aux field in front of its first
+ *           CG, or whose first CG is an array that leaves the record
+ *   8       a counted record whose reference end -- pos + the lengths of its M, D, N, =, X ops -- lies beyond ref_len[refID]
+ * Any -> PLO_ERR_INVALID_ARG, err_record the LOWEST such record, err_kind what it broke, plo_last_error names both, and A REFUSED CALL ADDS
+ * NOTHING: the add kernel reads the check's word first.
+ * plo_depth_create allocates and zeroes the array on ctx's device (ctx only names the device and takes the error text).  opts NULL: the
+ * defaults.  n_ref == 0 is allowed (an empty array); a negative ref_len -> PLO_ERR_INVALID_ARG.
+ * plo_depth_add_dev runs on the CALLING context's stream with that context's scratch (8 bytes a record) and returns when its kernels are
+ * through: a check (a wave per record) and the add (a wave per record: the ops a lane each, 64 a trip; a wave prefix sum of the reference
+ * lengths gives every op its start, ballots find the ends of every maximal covered stretch, ONE int32 atomic add of device scope per end:
+ * two a record for an = / X CIGAR without deletions).  The adds commute, so the array does not depend on the order of records, calls or
+ * contexts, and adds from several contexts of the same device may overlap in time.  A context of another device -> PLO_ERR_INVALID_ARG;
+ * more than 2^27 - 1 records in one call -> PLO_ERR_RANGE.
+ * plo_depth_finish_dev turns the differences into depths in place: ONE inclusive 32-bit scan over the whole array (every slot's
+ * differences sum to zero, so it equals a scan per chromosome) as tile sums, a scan of the sums, apply -- five launches, none of which
+ * waits on another workgroup.
+ * plo_depth_windows_dev: for a window size w >= 1 chromosome r has ceil(ref_len[r] / w) windows, the last one short; the uint64 sum of
+ * depths of every window and the table win_first[n_ref + 1] come down in the call's one wait, as HOST arrays owned by the object until its
+ * next windows call.  One launch.
+ * plo_depth_runs_dev: the per-base bedGraph.  A run is a maximal stretch of equal depth within a chromosome, zero-depth runs included; runs
+ * never cross a chromosome, a chromosome of length 0 has none; they are ordered by (ref_id, beg).  The runs stay on the DEVICE, owned by the
+ * object until its next runs call (16 bytes a run).
+ * plo_depth_reset zeroes the array and reopens the object.
+ * ORDER.  The object is open (adds, then one finish) or finished (windows, runs).  An add or a finish on a finished object, windows or runs
+ * on an open one -> PLO_ERR_INVALID_ARG.  finish, windows, runs, reset and destroy MUST NOT OVERLAP AN ADD on any context: that is the
+ * caller's duty (join the adding threads first); the object does not lock.
+ * plo_depth_info_get hands out the array and its entry count, so that a caller with several devices can sum the difference arrays of their
+ * objects before the finish (the summing itself is the caller's). */
+#define PLO_DEPTH_EXCLUDE_DEFAULT 0x704u
+
+typedef struct plo_depth plo_depth;
+
+typedef struct plo_depth_opts {
+    uint32_t exclude_flags;       /* a record with any of these FLAG bits is not counted */
+    int32_t count_deletions;      /* != 0: D covers its bases */
+} plo_depth_opts;
+
+typedef struct plo_depth_info {
+    int32_t *array;               /* device [n_entries]: differences while the object is open, depths once it is finished */
+    uint64_t n_entries;           /* slot_off[n_ref] */
+    const uint64_t *slot_off;     /* HOST [n_ref + 1], owned by the object */
+    uint64_t bytes_allocated;     /* device bytes the object holds now: the array, the scan's sums, its tables, windows and runs */
+    uint32_t n_ref;
+    uint32_t exclude_flags;
+    int32_t count_deletions;
+    int32_t finished;
+} plo_depth_info;
+
+typedef struct plo_depth_in {
+    const uint8_t *bytes;         /* device: records, each prefixed by its block_size, in any order */
+    uint64_t n_bytes;
+    uint32_t n_records;
+    const uint64_t *record_off;   /* device [n_records + 1] */
+} plo_depth_in;
+
+typedef struct plo_depth_add_out {
+    uint32_t n_records;
+    uint32_t n_counted;           /* records the rule counts */
+    uint32_t err_record;          /* PLO_ERR_INVALID_ARG from the device check: lowest offending record, else UINT32_MAX */
+    uint32_t err_kind;            /* what it broke (1 .. 8 above), else 0 */
+    float add_ms;                 /* HIP-event time of the call's two kernels */
+} plo_depth_add_out;
+
+typedef struct plo_depth_windows_out {
+    const uint64_t *sum;          /* HOST [n_windows]: the sum of the depths of every window */
+    const uint64_t *win_first;    /* HOST [n_ref + 1]: the first window of every chromosome; [n_ref] = n_windows */
+    uint64_t n_windows;
+    float windows_ms;
+} plo_depth_windows_out;
+
+typedef struct plo_depth_run {
+    int32_t ref_id;
+    int32_t beg, end;             /* 0-based half-open */
+    int32_t depth;
+} plo_depth_run;
+
+typedef struct plo_depth_runs_out {
+    const plo_depth_run *run;     /* device [n_runs], ordered by (ref_id, beg) */
+    uint64_t n_runs;
+    float runs_ms;
+} plo_depth_runs_out;
+
+plo_status plo_depth_create(plo_ctx *ctx, uint32_t n_ref, const int32_t *ref_len, const plo_depth_opts *opts, plo_depth **out);
+void plo_depth_destroy(plo_depth *depth);
+plo_status plo_depth_info_get(const plo_depth *depth, plo_depth_info *info);
+plo_status plo_depth_add_dev(plo_ctx *ctx, plo_depth *depth, const plo_depth_in *in, plo_depth_add_out *out);
+plo_status plo_depth_finish_dev(plo_ctx *ctx, plo_depth *depth, float *finish_ms);
+plo_status plo_depth_windows_dev(plo_ctx *ctx, plo_depth *depth, uint32_t window, plo_depth_windows_out *out);
+plo_status plo_depth_runs_dev(plo_ctx *ctx, plo_depth *depth, plo_depth_runs_out *out);
+plo_status plo_depth_reset(plo_ctx *ctx, plo_depth *depth);
 
 /* ---- Sorted windows merged into large runs (device-resident, opt-in; API version 18) --------------------------------------
  * A k-way merge of coordinate-sorted record buffers -- typically copies of plo_sort_out::bytes / record_off of several windows -- that each

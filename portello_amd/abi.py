@@ -136,7 +136,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 18  # include/portello_liftover.h
+PLO_API_VERSION = 19  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -262,6 +262,44 @@ class PloIndexIn(C.Structure):
 class PloIndexOut(C.Structure):
     _fields_ = [("entry", C.POINTER(PloIndexEntry)), ("n_records", C.c_uint32), ("n_placed", C.c_uint32), ("err_record", C.c_uint32), ("err_kind", C.c_uint32),
                 ("index_ms", C.c_float)]
+
+
+DEPTH_EXCLUDE_DEFAULT = 0x704  # PLO_DEPTH_EXCLUDE_DEFAULT: unmapped, secondary, QC-fail, duplicate
+
+
+class PloDepthOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_uint32), ("count_deletions", C.c_int32)]
+
+
+class PloDepthInfo(C.Structure):
+    """array: device; slot_off: HOST [n_ref + 1]"""
+    _fields_ = [("array", C.POINTER(C.c_int32)), ("n_entries", C.c_uint64), ("slot_off", _u64p), ("bytes_allocated", C.c_uint64), ("n_ref", C.c_uint32),
+                ("exclude_flags", C.c_uint32), ("count_deletions", C.c_int32), ("finished", C.c_int32)]
+
+
+class PloDepthIn(C.Structure):
+    _fields_ = [("bytes", _u8p), ("n_bytes", C.c_uint64), ("n_records", C.c_uint32), ("record_off", _u64p)]
+
+
+class PloDepthAddOut(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("n_counted", C.c_uint32), ("err_record", C.c_uint32), ("err_kind", C.c_uint32), ("add_ms", C.c_float)]
+
+
+class PloDepthWindowsOut(C.Structure):
+    """sum / win_first are HOST arrays of n_windows and n_ref + 1 values"""
+    _fields_ = [("sum", _u64p), ("win_first", _u64p), ("n_windows", C.c_uint64), ("windows_ms", C.c_float)]
+
+
+class PloDepthRun(C.Structure):
+    """16 bytes: ref_id, [beg, end), depth"""
+    _fields_ = [("ref_id", C.c_int32), ("beg", C.c_int32), ("end", C.c_int32), ("depth", C.c_int32)]
+
+
+DEPTH_RUN_DTYPE = np.dtype([("ref_id", "<i4"), ("beg", "<i4"), ("end", "<i4"), ("depth", "<i4")])  # plo_depth_run as a numpy record
+
+
+class PloDepthRunsOut(C.Structure):
+    _fields_ = [("run", C.POINTER(PloDepthRun)), ("n_runs", C.c_uint64), ("runs_ms", C.c_float)]
 
 
 class PloEqxOut(C.Structure):

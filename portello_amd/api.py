@@ -88,6 +88,22 @@ def load_library(path: Optional[str] = None):
     L.plo_runs_merge_emit_dev.argtypes = [vp, C.c_uint32, C.POINTER(abi.PloMergeChunkOut)]
     L.plo_records_index_dev.restype = C.c_int
     L.plo_records_index_dev.argtypes = [vp, C.POINTER(abi.PloIndexIn), C.POINTER(abi.PloIndexOut)]
+    L.plo_depth_create.restype = C.c_int
+    L.plo_depth_create.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(abi.PloDepthOpts), C.POINTER(vp)]
+    L.plo_depth_destroy.restype = None
+    L.plo_depth_destroy.argtypes = [vp]
+    L.plo_depth_info_get.restype = C.c_int
+    L.plo_depth_info_get.argtypes = [vp, C.POINTER(abi.PloDepthInfo)]
+    L.plo_depth_add_dev.restype = C.c_int
+    L.plo_depth_add_dev.argtypes = [vp, vp, C.POINTER(abi.PloDepthIn), C.POINTER(abi.PloDepthAddOut)]
+    L.plo_depth_finish_dev.restype = C.c_int
+    L.plo_depth_finish_dev.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.plo_depth_windows_dev.restype = C.c_int
+    L.plo_depth_windows_dev.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.PloDepthWindowsOut)]
+    L.plo_depth_runs_dev.restype = C.c_int
+    L.plo_depth_runs_dev.argtypes = [vp, vp, C.POINTER(abi.PloDepthRunsOut)]
+    L.plo_depth_reset.restype = C.c_int
+    L.plo_depth_reset.argtypes = [vp, vp]
     L.plo_eqx_dev.restype = C.c_int
     L.plo_eqx_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloEqxOut)]
     L.plo_records_build_dev.restype = C.c_int

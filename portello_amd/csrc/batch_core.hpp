@@ -293,6 +293,22 @@ PLO_DEV void bb_primary(const uint8_t *p, const uint8_t *cig, uint32_t n_cig, ui
     g.ctext = g.ctext_end = nullptr;
 }
 
+// real_cigar (:966-979), shared with depth_core.hpp.  The in-record CIGAR (n_cig ops at cig, inside the record) is the placeholder
+// <l_seq>S<n>N that bam_write1 leaves behind more than 65 535 ops
+PLO_DEV bool bb_cigar_is_placeholder(const uint8_t *cig, uint32_t n_cig, uint32_t lseq) {
+    if (n_cig != 2) return false;
+    const unsigned c0 = rec_rd32(cig), c1 = rec_rd32(cig + 4);
+    return (c0 & 15u) == 4 && (c0 >> 4) == lseq && (c1 & 15u) == 3;
+}
+// cig / n_cig: the in-record CIGAR on entry, the record's real CIGAR on return -- the ops of the field cg (the record's first CG field,
+// complete inside the record, or NULL) when that is a B,I array and the in-record CIGAR is the placeholder
+PLO_DEV void bb_real_cigar(const uint8_t *cg, uint32_t lseq, const uint8_t *&cig, uint32_t &n_cig) {
+    if (cg && cg[2] == 'B' && cg[3] == 'I' && bb_cigar_is_placeholder(cig, n_cig, lseq)) {
+        n_cig = rec_rd32(cg + 4);
+        cig = cg + 8;
+    }
+}
+
 // ---- plan -------------------------------------------------------------------------------------------------------------------------------
 PLO_DEV void batch_plan_read(const DevBatchBuild &d, uint32_t r) {
     const bool lane0 = wv::lane() == 0;
@@ -341,16 +357,9 @@ PLO_DEV void batch_plan_read(const DevBatchBuild &d, uint32_t r) {
         }
         a += n;
     }
-    // real_cigar (:966-979)
     const uint8_t *cig = p + 32 + lq;
     uint32_t n_cig = ncg;
-    if (ncg == 2 && cg && cg[2] == 'B' && cg[3] == 'I') {
-        const unsigned c0 = rec_rd32(cig), c1 = rec_rd32(cig + 4);
-        if ((c0 & 15u) == 4 && (c0 >> 4) == lseq && (c1 & 15u) == 3) {
-            n_cig = rec_rd32(cg + 4);
-            cig = cg + 8;
-        }
-    }
+    bb_real_cigar(cg, lseq, cig, n_cig);
     SaSegment g;
     unsigned long long size = 0, n_ops = n_cig;
     bb_primary(p, cig, n_cig, nullptr, g, size);

@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -47,6 +48,7 @@
 #include "sort_core.hpp"
 #include "merge_core.hpp"
 #include "index_core.hpp"
+#include "depth_core.hpp"
 #define PLO_FA_HOST 1
 #include "fasta_core.hpp"
 #include "window_core.hpp"
@@ -1388,6 +1390,29 @@ __global__ __launch_bounds__(256) void k_merge_copy(DevMergeEmit d, unsigned lon
 // ---- index entries of the sorted records (index_core.hpp): a wave per record, the records grid-strided over the waves; no LDS
 __global__ __launch_bounds__(256) void k_index(DevBai d) { index_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
 
+// ---- depth of the records (depth_core.hpp): no LDS anywhere, no kernel waits on another workgroup -----------------------------------------
+// check and add: a wave per record, the records grid-strided over the waves.  The add is bound by its scattered atomics, one lane a cache line
+__global__ __launch_bounds__(256) void k_depth_check(DevDepth d) { depth_check_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+__global__ __launch_bounds__(256) void k_depth_add(DevDepth d) { depth_add_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+// the scan: a wave per tile of PLO_DEPTH_TILE entries.  HBM-bound by design: the array is read by the sums, read and written by the apply
+__global__ __launch_bounds__(256) void k_depth_sums(const int32_t *a, unsigned long long n, unsigned long long n_tiles, int32_t *sums) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id();
+    if (t < n_tiles) depth_tile_sum(a, n, t, sums);  // (wave-uniform)
+}
+__global__ __launch_bounds__(256) void k_depth_apply(int32_t *a, unsigned long long n, unsigned long long n_tiles, const int32_t *incl) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id();
+    if (t < n_tiles) depth_tile_scan(a, n, t, incl);
+}
+__global__ __launch_bounds__(64) void k_depth_top(int32_t *a, unsigned long long n) { depth_top_scan(a, n); }
+__global__ __launch_bounds__(256) void k_depth_windows(DevDepthWin d) {
+    depth_windows(d, (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id(), (unsigned long long)gridDim.x * 4u);
+}
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_depth_runs(DevDepthRuns d, unsigned long long n_tiles) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id();
+    if (t < n_tiles) depth_runs_tile<EMIT>(d, t);
+}
+
 // ---- the reference FASTA (fasta_core.hpp): a wave per tile of FA_TILE bytes, the tiles grid-strided over the waves; no LDS.  HBM-bound by
 // design: the piece is read by k_fa_lines, k_fa_count and k_fa_emit (k_fa_headers leaves the tiles without a header line alone), the bases
 // are written once
@@ -1683,6 +1708,25 @@ struct plo_fasta {
     std::vector<void *> adopted;
 };
 
+// plo_depth_*: the depth array of a list of chromosomes (depth_core.hpp).  An object of its own: several contexts add to it.
+struct plo_depth {
+    int device = 0;
+    uint32_t n_ref = 0;
+    uint32_t exclude_flags = PLO_DEPTH_EXCLUDE_DEFAULT;
+    int count_del = 0;
+    std::atomic<bool> finished{false};
+    std::vector<int32_t> ref_len;
+    std::vector<uint64_t> slot_off;  // [n_ref + 1]
+    unsigned long long n_entries = 0, n1 = 0, n2 = 0;  // entries, their tiles, the tiles of the tiles' sums
+    DevBuf arr, d_ref_len, d_slot_off, s1, s2, win_first, win_sum, run_cnt, run_start, run_partial, runs;
+    HostBuf h_win;  // win_first [n_ref + 1], then the sums
+    size_t bytes() const {
+        size_t b = 0;
+        for (const DevBuf *x : {&arr, &d_ref_len, &d_slot_off, &s1, &s2, &win_first, &win_sum, &run_cnt, &run_start, &run_partial, &runs}) b += x->cap;
+        return b;
+    }
+};
+
 struct plo_ctx {
     const plo_index *ix = nullptr;
     hipStream_t stream = nullptr;
@@ -1734,6 +1778,10 @@ struct plo_ctx {
     DevBuf bai_entry, bai_blk;
     HostBuf h_bai;
     hipEvent_t xev[2] = {nullptr, nullptr};
+    // plo_depth_add_dev: the plan word of every record and the call's two words (lowest offender << 4 | kind, n_counted); dpev: every plo_depth_* call
+    DevBuf dp_plan, dp_blk;
+    HostBuf h_dp;
+    hipEvent_t dpev[2] = {nullptr, nullptr};
     bool rec_bytecopy = false;  // PLO_RECORDS_BYTECOPY=1: plo_records_build_dev moves every byte on its own (k_rec_emit<false>, the A/B of the 16-byte copy)
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2370,7 +2418,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
                       &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk, &c->eqx_len, &c->eqx_off, &c->eqx_partial, &c->eqx_ops, &c->eqx_blk,
-                      &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk,
+                      &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk, &c->dp_plan, &c->dp_blk,
                       &c->mg_key[0], &c->mg_key[1], &c->mg_src[0], &c->mg_src[1], &c->mg_runof, &c->mg_len, &c->mg_mlen, &c->mg_off, &c->mg_partial, &c->mg_runs, &c->mg_first, &c->mg_blk, &c->mg_cfirst,
                       &c->mg_coff, &c->mg_out, &c->mg_ooff,
                       &c->item_region, &c->lane_groups, &c->lane_ticket, &c->misc, &c->whist, &c->cls_partial, &c->lane_scratch, &c->item_cls, &c->retry_list, &c->perm, &c->nin_p, &c->seg_reflen, &c->seg_readlen, &c->seg_nm, &c->seg_cnt, &c->seg_off, &c->scan_partial, &c->item_seg, &c->item_cseg, &c->item_nin, &c->op_prefix,
@@ -2382,7 +2430,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai, &c->h_mg, &c->h_mg_tab};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai, &c->h_dp, &c->h_mg, &c->h_mg_tab};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2408,6 +2456,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->xev[i]) (void)hipEventDestroy(c->xev[i]);
+    for (int i = 0; i < 2; ++i)
+        if (c->dpev[i]) (void)hipEventDestroy(c->dpev[i]);
     for (int i = 0; i < 4; ++i)
         if (c->gev[i]) (void)hipEventDestroy(c->gev[i]);
     if (c->ev_seq) (void)hipEventDestroy(c->ev_seq);
@@ -4401,6 +4451,299 @@ plo_status plo_records_index_dev(plo_ctx *c, const plo_index_in *in, plo_index_o
     (void)hipEventElapsedTime(&out->index_ms, c->xev[0], c->xev[1]);
     out->n_records = n;
     out->n_placed = h[1];
+    return PLO_OK;
+}
+
+// ---- plo_depth_* (depth_core.hpp) -------------------------------------------------------------------------------------------------------------
+// the array, exactly its size (a DevBuf would round 12 GB up by a quarter), zeroed; the tables; the sums of the scan
+plo_status plo_depth_create(plo_ctx *c, uint32_t n_ref, const int32_t *ref_len, const plo_depth_opts *opts, plo_depth **out) {
+    if (!c || !out || (n_ref && !ref_len)) return PLO_ERR_INVALID_ARG;
+    *out = nullptr;
+    c->err.clear();
+    if (n_ref > 0x7fffffffu) {
+        c->err = "plo_depth_create: more than 2^31 - 1 references";
+        return PLO_ERR_RANGE;
+    }
+    for (uint32_t r = 0; r < n_ref; ++r)
+        if (ref_len[r] < 0) {
+            c->err = "plo_depth_create: ref_len[" + std::to_string(r) + "] is negative";
+            return PLO_ERR_INVALID_ARG;
+        }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    plo_depth *d = new plo_depth();
+    d->device = c->ix->device;
+    d->n_ref = n_ref;
+    if (opts) {
+        d->exclude_flags = opts->exclude_flags;
+        d->count_del = opts->count_deletions != 0;
+    }
+    d->ref_len.assign(ref_len, ref_len + n_ref);
+    d->slot_off.resize((size_t)n_ref + 1);
+    d->n_entries = depth_layout(n_ref, d->ref_len.data(), d->slot_off.data());
+    d->n1 = (d->n_entries + DEPTH_TILE - 1) / DEPTH_TILE;
+    d->n2 = (d->n1 + DEPTH_TILE - 1) / DEPTH_TILE;
+    const size_t arr_bytes = std::max<size_t>((size_t)d->n_entries * 4, 16);
+    hipError_t e = hipMalloc(&d->arr.p, arr_bytes);
+    if (e == hipSuccess) d->arr.cap = arr_bytes;
+    if (e == hipSuccess) e = d->d_ref_len.ensure(std::max<size_t>((size_t)n_ref * 4, 16));
+    if (e == hipSuccess) e = d->d_slot_off.ensure(((size_t)n_ref + 1) * 8);
+    if (e == hipSuccess) e = d->s1.ensure(std::max<size_t>((size_t)d->n1 * 4, 16));
+    if (e == hipSuccess) e = d->s2.ensure(std::max<size_t>((size_t)d->n2 * 4, 16));
+    if (e == hipSuccess) e = hipMemsetAsync(d->arr.p, 0, arr_bytes, c->stream);
+    if (e == hipSuccess && n_ref) e = hipMemcpyAsync(d->d_ref_len.p, d->ref_len.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->d_slot_off.p, d->slot_off.data(), ((size_t)n_ref + 1) * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        c->err = std::string("plo_depth_create: ") + hipGetErrorString(e) + " (" + std::to_string(arr_bytes) + " bytes for " + std::to_string(d->n_entries) + " entries)";
+        plo_depth_destroy(d);
+        return e == hipErrorOutOfMemory ? PLO_ERR_OUT_OF_MEMORY : PLO_ERR_HIP;
+    }
+    *out = d;
+    return PLO_OK;
+}
+
+void plo_depth_destroy(plo_depth *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    for (DevBuf *b : {&d->arr, &d->d_ref_len, &d->d_slot_off, &d->s1, &d->s2, &d->win_first, &d->win_sum, &d->run_cnt, &d->run_start, &d->run_partial, &d->runs}) b->release();
+    d->h_win.release();
+    delete d;
+}
+
+plo_status plo_depth_info_get(const plo_depth *d, plo_depth_info *info) {
+    if (!d || !info) return PLO_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    info->array = d->arr.as<int32_t>();
+    info->n_entries = d->n_entries;
+    info->slot_off = d->slot_off.data();
+    info->bytes_allocated = d->bytes();
+    info->n_ref = d->n_ref;
+    info->exclude_flags = d->exclude_flags;
+    info->count_deletions = d->count_del;
+    info->finished = d->finished.load() ? 1 : 0;
+    return PLO_OK;
+}
+
+// what every plo_depth_* call on a context begins with: the object is of the context's device and in a state that admits the call
+static plo_status depth_enter(plo_ctx *c, plo_depth *d, int call, const char *name) {
+    c->err.clear();
+    if (d->device != c->ix->device) {
+        c->err = std::string(name) + ": the depth object lives on device " + std::to_string(d->device) + ", the context on device " + std::to_string(c->ix->device);
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (!depth_call_allowed(d->finished.load(), call)) {
+        c->err = std::string(name) + (d->finished.load() ? ": the depth object is finished (plo_depth_reset reopens it)" : ": the depth object is not finished (plo_depth_finish_dev)");
+        return PLO_ERR_INVALID_ARG;
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    for (int i = 0; i < 2; ++i)
+        if (!c->dpev[i]) HIP_TRY(c, hipEventCreate(&c->dpev[i]));
+    return PLO_OK;
+}
+
+// The check and the add (depth_core.hpp): two launches on the context's stream, a wave per record, at most 2048 workgroups of four waves; the
+// call's two words come back behind them, one wait.  The add reads the check's word first.
+plo_status plo_depth_add_dev(plo_ctx *c, plo_depth *dp, const plo_depth_in *in, plo_depth_add_out *out) {
+    if (!c || !dp || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_record = UINT32_MAX;
+    plo_status ps = depth_enter(c, dp, DEPTH_CALL_ADD, "plo_depth_add_dev");
+    if (ps != PLO_OK) return ps;
+    const uint32_t n = in->n_records;
+    if (n && (!in->bytes || !in->record_off)) {
+        c->err = "plo_depth_in: the records and their offsets are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (n > DEPTH_MAX_RECORDS) {
+        c->err = "plo_depth_add_dev: more than 2^27 - 1 records";
+        return PLO_ERR_RANGE;
+    }
+    if (!n) return PLO_OK;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->dp_plan.ensure((size_t)n * 8));
+    HIP_TRY(c, c->dp_blk.ensure(16));
+    HIP_TRY(c, c->h_dp.ensure(16));
+    DevDepth d;
+    memset(&d, 0, sizeof(d));
+    d.s.bytes = in->bytes;
+    d.s.n_bytes = in->n_bytes;
+    d.s.n = n;
+    d.s.record_off = in->record_off;
+    d.s.n_ref = dp->n_ref;
+    d.ref_len = dp->d_ref_len.as<int32_t>();
+    d.slot_off = dp->d_slot_off.as<uint64_t>();
+    d.arr = dp->arr.as<int32_t>();
+    d.exclude_flags = dp->exclude_flags;
+    d.count_del = dp->count_del;
+    d.plan = c->dp_plan.as<uint64_t>();
+    d.err = c->dp_blk.as<int>();
+    d.n_counted = c->dp_blk.as<unsigned>() + 1;
+    uint32_t *h = c->h_dp.as<uint32_t>();
+    h[0] = (uint32_t)DEPTH_NO_RECORD;
+    h[1] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->dp_blk.p, h, 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    const dim3 grid(std::min(2048u, (n + 3u) / 4u));
+    hipLaunchKernelGGL(k_depth_check, grid, dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_depth_add, grid, dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->dp_blk.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)DEPTH_NO_RECORD) {
+        static const char *const what[] = {"", "record_off: it must start at 0, not decrease and end at n_bytes", "its length: fewer than the 36 bytes of block_size and the fixed fields",
+                                           "block_size: block_size + 4 differs from the record's length", "refID: outside [-1, n_ref)", "pos: outside [-1, 2^31 - 2]",
+                                           "its CIGAR: 36 + l_read_name + 4 n_cigar_op passes the record's end",
+                                           "its aux fields: the CIGAR is the placeholder <l_seq>S<n>N, and the fields begin behind the record's end, one in front of the first CG is malformed, or that CG leaves the record",
+                                           "its end: the record is counted and reaches beyond ref_len[refID]"};
+        out->err_record = h[0] >> 4;
+        out->err_kind = h[0] & 15u;
+        c->err = "plo_depth_add_dev: record " + std::to_string(out->err_record) + " is refused for " + (out->err_kind >= 1 && out->err_kind <= 8 ? what[out->err_kind] : "an unknown reason") +
+                 "; nothing was added";
+        return PLO_ERR_INVALID_ARG;
+    }
+    (void)hipEventElapsedTime(&out->add_ms, c->dpev[0], c->dpev[1]);
+    out->n_records = n;
+    out->n_counted = h[1];
+    return PLO_OK;
+}
+
+// tile sums -> their sums -> one wave scans those -> the tiles of the sums -> the tiles of the array
+plo_status plo_depth_finish_dev(plo_ctx *c, plo_depth *dp, float *finish_ms) {
+    if (!c || !dp) return PLO_ERR_INVALID_ARG;
+    if (finish_ms) *finish_ms = 0.f;
+    plo_status ps = depth_enter(c, dp, DEPTH_CALL_FINISH, "plo_depth_finish_dev");
+    if (ps != PLO_OK) return ps;
+    hipStream_t st = c->stream;
+    const unsigned long long n0 = dp->n_entries, n1 = dp->n1, n2 = dp->n2;
+    if (n1 + 3 > 0x7fffffffull * 4ull) {
+        c->err = "plo_depth_finish_dev: more tiles than a launch has workgroups";
+        return PLO_ERR_RANGE;
+    }
+    int32_t *a = dp->arr.as<int32_t>(), *s1 = dp->s1.as<int32_t>(), *s2 = dp->s2.as<int32_t>();
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    if (n0) {
+        const dim3 g1((unsigned)((n1 + 3) / 4)), g2((unsigned)((n2 + 3) / 4));
+        hipLaunchKernelGGL(k_depth_sums, g1, dim3(256), 0, st, (const int32_t *)a, n0, n1, s1);
+        hipLaunchKernelGGL(k_depth_sums, g2, dim3(256), 0, st, (const int32_t *)s1, n1, n2, s2);
+        hipLaunchKernelGGL(k_depth_top, dim3(1), dim3(64), 0, st, s2, n2);
+        hipLaunchKernelGGL(k_depth_apply, g2, dim3(256), 0, st, s1, n1, n2, (const int32_t *)s2);
+        hipLaunchKernelGGL(k_depth_apply, g1, dim3(256), 0, st, a, n0, n1, (const int32_t *)s1);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (finish_ms) (void)hipEventElapsedTime(finish_ms, c->dpev[0], c->dpev[1]);
+    dp->finished.store(true);
+    return PLO_OK;
+}
+
+// one launch; the table is the host's (ref_len is), the sums come down behind the kernel, one wait
+plo_status plo_depth_windows_dev(plo_ctx *c, plo_depth *dp, uint32_t window, plo_depth_windows_out *out) {
+    if (!c || !dp || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    plo_status ps = depth_enter(c, dp, DEPTH_CALL_WINDOWS, "plo_depth_windows_dev");
+    if (ps != PLO_OK) return ps;
+    if (!window) {
+        c->err = "plo_depth_windows_dev: the window size must be 1 or more";
+        return PLO_ERR_INVALID_ARG;
+    }
+    hipStream_t st = c->stream;
+    const size_t nt = (size_t)dp->n_ref + 1;
+    std::vector<uint64_t> first(nt);
+    const unsigned long long n_win = depth_win_layout(dp->n_ref, dp->ref_len.data(), window, first.data());
+    HIP_TRY(c, dp->h_win.ensure((nt + (size_t)n_win) * 8));
+    HIP_TRY(c, dp->win_first.ensure(nt * 8));
+    HIP_TRY(c, dp->win_sum.ensure(std::max<size_t>((size_t)n_win * 8, 16)));
+    uint64_t *h = dp->h_win.as<uint64_t>();
+    memcpy(h, first.data(), nt * 8);
+    HIP_TRY(c, hipMemcpyAsync(dp->win_first.p, h, nt * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    if (n_win) {
+        DevDepthWin d;
+        memset(&d, 0, sizeof(d));
+        d.arr = dp->arr.as<int32_t>();
+        d.ref_len = dp->d_ref_len.as<int32_t>();
+        d.slot_off = dp->d_slot_off.as<uint64_t>();
+        d.win_first = dp->win_first.as<uint64_t>();
+        d.n_ref = dp->n_ref;
+        d.w = window;
+        d.n_win = n_win;
+        d.sum = dp->win_sum.as<uint64_t>();
+        const unsigned long long waves = window >= 64 ? n_win : (n_win + 63) / 64;
+        hipLaunchKernelGGL(k_depth_windows, dim3((unsigned)std::min<unsigned long long>(16384, (waves + 3) / 4)), dim3(256), 0, st, d);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    if (n_win) HIP_TRY(c, hipMemcpyAsync(h + nt, dp->win_sum.p, (size_t)n_win * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->windows_ms, c->dpev[0], c->dpev[1]);
+    out->sum = h + nt;
+    out->win_first = h;
+    out->n_windows = n_win;
+    return PLO_OK;
+}
+
+// run starts per tile, the 64-bit scan (records_core.hpp), the count comes down (the runs are sized by it), emit
+plo_status plo_depth_runs_dev(plo_ctx *c, plo_depth *dp, plo_depth_runs_out *out) {
+    if (!c || !dp || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    plo_status ps = depth_enter(c, dp, DEPTH_CALL_RUNS, "plo_depth_runs_dev");
+    if (ps != PLO_OK) return ps;
+    static_assert(sizeof(plo_depth_run) == sizeof(DepthRun) && offsetof(plo_depth_run, depth) == offsetof(DepthRun, depth), "plo_depth_run and DepthRun are one layout");
+    hipStream_t st = c->stream;
+    const unsigned long long n_tiles = dp->n1;
+    if (!n_tiles) return PLO_OK;
+    if (n_tiles > 0xffffffffull) {
+        c->err = "plo_depth_runs_dev: more than 2^32 - 1 tiles";
+        return PLO_ERR_RANGE;
+    }
+    const uint32_t nt = (uint32_t)n_tiles, nb = (nt + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK;
+    HIP_TRY(c, dp->run_cnt.ensure((size_t)nt * 8));
+    HIP_TRY(c, dp->run_start.ensure(((size_t)nt + 1) * 8));
+    HIP_TRY(c, dp->run_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->h_dp.ensure(16));
+    DevDepthRuns d;
+    memset(&d, 0, sizeof(d));
+    d.arr = dp->arr.as<int32_t>();
+    d.ref_len = dp->d_ref_len.as<int32_t>();
+    d.slot_off = dp->d_slot_off.as<uint64_t>();
+    d.n_ref = dp->n_ref;
+    d.n_entries = dp->n_entries;
+    d.cnt = dp->run_cnt.as<unsigned long long>();
+    d.start = dp->run_start.as<unsigned long long>();
+    unsigned long long *start = dp->run_start.as<unsigned long long>();
+    const dim3 grid((nt + 3u) / 4u);
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    hipLaunchKernelGGL(k_depth_runs<false>, grid, dim3(256), 0, st, d, n_tiles);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, dp->run_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, dp->run_partial.as<unsigned long long>(), nt, nb, start);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, (const unsigned long long *)dp->run_partial.as<unsigned long long>(), start);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *h = c->h_dp.as<unsigned long long>();
+    HIP_TRY(c, hipMemcpyAsync(h, start + nt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const unsigned long long n_runs = h[0];
+    HIP_TRY(c, dp->runs.ensure(std::max<size_t>((size_t)n_runs * sizeof(DepthRun), 16)));
+    d.run = dp->runs.as<DepthRun>();
+    hipLaunchKernelGGL(k_depth_runs<true>, grid, dim3(256), 0, st, d, n_tiles);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->runs_ms, c->dpev[0], c->dpev[1]);
+    out->run = dp->runs.as<plo_depth_run>();
+    out->n_runs = n_runs;
+    return PLO_OK;
+}
+
+plo_status plo_depth_reset(plo_ctx *c, plo_depth *dp) {
+    if (!c || !dp) return PLO_ERR_INVALID_ARG;
+    plo_status ps = depth_enter(c, dp, DEPTH_CALL_RESET, "plo_depth_reset");
+    if (ps != PLO_OK) return ps;
+    if (dp->n_entries) HIP_TRY(c, hipMemsetAsync(dp->arr.p, 0, (size_t)dp->n_entries * 4, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dp->finished.store(false);
     return PLO_OK;
 }
 

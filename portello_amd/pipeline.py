@@ -78,6 +78,8 @@ class PipelineStats:
     merge_plan_device_ms: float = 0.0  # run_windows != 1: HIP-event time of plo_runs_merge_plan_dev (check + keys, rank rounds, offsets, chunk table)
     merge_emit_device_ms: float = 0.0  # run_windows != 1: HIP-event time of plo_runs_merge_emit_dev, summed over the chunks
     run_groups: List[int] = field(default_factory=list)  # sorted_runs: the windows with records in every written run, in out_paths order (all 1 with run_windows=1)
+    depth_device_ms: float = 0.0  # depth_out: HIP-event time of plo_depth_add_dev over the windows, plus the finish, the windows and the runs
+    depth_paths: List[str] = field(default_factory=list)  # depth_out: <prefix>.per-base.bed and <prefix>.regions.bed
     sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
@@ -95,8 +97,19 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
                    device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False,
                    index_runs: bool = False, emit_eqx: bool = False, run_windows: int = 1, run_budget_bytes: Optional[int] = None,
-                   run_chunk_bytes: int = 1 << 30) -> PipelineStats:  # noqa: E501
-    """run_windows (default 1; anything else needs sorted_runs=True): how many windows leave as one run.  1: every window is a run of its
+                   run_chunk_bytes: int = 1 << 30, depth_out: Optional[str] = None, depth_window: int = 500, depth_deletions: bool = False) -> PipelineStats:  # noqa: E501
+    """depth_out (default None; a path prefix; needs device_records=True): the depth of the output records is taken while they lie on the
+    device, so that no mosdepth or `samtools depth` pass has to read the written file back.  The process holds ONE depth object
+    (depth.DeviceDepth over ref_lens: 4 bytes a reference base); every lift worker adds its window's plo_records_out right behind
+    plo_records_build_dev (plo_depth_add_dev on the worker's own context and stream: the adds are integer atomics, so neither the order of
+    the windows nor the number of workers changes a value).  When the workers are joined the differences become depths
+    (plo_depth_finish_dev) and two files are written: <prefix>.per-base.bed (chrom, beg, end, depth: maximal runs of equal depth, zero
+    ones too) and <prefix>.regions.bed (chrom, beg, end, mean over windows of depth_window bases, two decimals, round-half-even).  The
+    counting rule is mosdepth's and samtools depth's flag mask 0x704 over the records' real CIGARs; depth_deletions=True lets D cover its
+    bases (mosdepth, `samtools depth -J`), False (default) is `samtools depth`.  PipelineStats: depth_device_ms, depth_paths.  Combines
+    with every other output switch (the unsorted records are added, so sorted_runs makes no difference); with depth_out=None every byte
+    of every output is what it was.
+    run_windows (default 1; anything else needs sorted_runs=True): how many windows leave as one run.  1: every window is a run of its
     own, as below -- same file names, same bytes, no new allocation.  K > 1: the windows [mK, (m + 1)K) of a reader, by the reader's window
     sequence number and not by arrival at the lift workers, form group m.  Every worker keeps its sorted window on the device
     (devbatch.RetainedWindow: a device-to-device copy of plo_sort_out) and hands it to ONE merger thread with a context of its own on the
@@ -187,6 +200,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     # time: half of io_threads each by default (tools/bench_e2e_threads.py on the 16-core GPU box, best of three runs: 80.6-81.4 k reads/s
     # with 8 / 4-8 / 6-8 threads against 77.1 k with 16 each; the input and output stages are bound by the page cache either way)
     run_windows = int(run_windows)
+    if depth_out is not None and not device_records:
+        raise ValueError("depth_out adds the records plo_records_build_dev leaves on the device: it needs device_records=True")
+    if depth_out is not None and int(depth_window) < 1:
+        raise ValueError("depth_window is the size of the windows of <prefix>.regions.bed in bases: it must be 1 or more")
     if run_windows != 1 and not sorted_runs:
         raise ValueError("run_windows merges the coordinate-sorted windows of a group into one run: it needs sorted_runs=True")
     if run_windows < 0:
@@ -274,6 +291,17 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
             except queue.Empty:
                 pass
         return None
+
+    depth_box = [None]  # depth_out: the process's one depth object, made by the first lift worker that has a context
+    depth_lock = threading.Lock()
+
+    def depth_object(eng):
+        from . import depth as _depth
+
+        with depth_lock:
+            if depth_box[0] is None:
+                depth_box[0] = _depth.DeviceDepth(eng, ref_lens, count_deletions=depth_deletions)
+            return depth_box[0]
 
     merge_windows = sorted_runs and run_windows != 1
     if merge_windows:
@@ -508,6 +536,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                                 marks.append(("eqx", time.perf_counter()))
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
+                            depth_ms = 0.0
+                            if depth_out is not None and ro.n_records:
+                                depth_ms = float(depth_object(eng).add(eng, ro.bytes, ro.n_bytes, ro.n_records, ro.record_off).add_ms)
+                                marks.append(("depth", time.perf_counter()))
                             srt, sort_ms = None, 0.0
                             if sorted_runs and ro.n_records:
                                 srt = eng.records_sort_dev(ro.bytes, ro.n_bytes, ro.n_records, ro.record_off, len(ref_names))
@@ -541,6 +573,7 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.md_device_ms += md_ms
                             st.eqx_device_ms += eqx_ms
                             st.sort_device_ms += sort_ms
+                            st.depth_device_ms += depth_ms
                             st.index_device_ms += index_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
@@ -664,6 +697,30 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         t_merger.start()
     for t in front:
         t.join()
+    if depth_out is not None and not st.errors:  # every add is through: the workers are joined
+        from . import depth as _depth
+
+        deng = None
+        try:
+            deng = api.Engine(index)
+            dobj = depth_object(deng)
+            ms = dobj.finish(deng)
+            win_first, win_sums, wms = dobj.windows(deng, int(depth_window))
+            runs_, rms = dobj.runs(deng, with_ms=True)
+            st.depth_device_ms += ms + wms + rms
+            st.depth_paths = [depth_out + ".per-base.bed", depth_out + ".regions.bed"]
+            _depth.write_per_base(st.depth_paths[0], ref_names, runs_)
+            _depth.write_regions(st.depth_paths[1], ref_names, [int(n) for n in ref_lens], int(depth_window), win_first, win_sums)
+        except BaseException as e:  # noqa: BLE001
+            st.errors.append(f"depth: {e!r}")
+            abort.set()
+        finally:
+            if depth_box[0] is not None:
+                depth_box[0].close()
+            if deng is not None:
+                deng.close()
+    elif depth_box[0] is not None:
+        depth_box[0].close()
     if merge_windows:
         with mcond:
             for ci in range(len(rds)):

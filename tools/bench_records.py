@@ -33,6 +33,9 @@ For a chr20 window of --reads reads held in memory, JSON with
     records_ms, and one device-to-device hipMemcpyAsync of the call's algorithmic read bytes (36 + 4 n_cigar_op a record) taken in the
     same process; the entries are compared with those computed on the host (numpy, from the rule) before anything is timed.  On the CPU:
     the writer's close with and without an index, and the merge of the window's two halves with and without one
+  - plo_depth_add_dev on the window's records (--depth-out; this leg runs alone): add_ms beside index_ms of the same records (the same walk
+    of every CIGAR without atomics), and finish_ms, windows_ms and runs_ms beside one device-to-device hipMemcpyAsync of the array's bytes
+    taken in the same process; differences, depths, window sums and the run count are compared with numpy's before anything is timed
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -49,6 +52,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --sort-out profiles/r14_sort_window.json
     python tools/bench_records.py --reads 50000 --index-out profiles/r15_index_window.json
     python tools/bench_records.py --reads 50000 --merge-out profiles/r18_merge_runs.json --merge-windows 4
+    python tools/bench_records.py --reads 50000 --depth-out profiles/r19_depth.json
 """
 import argparse
 import ctypes as C
@@ -923,6 +927,106 @@ def index_leg(a, win, index, cn, rn, rl, dev):
     return res, bool(same)
 
 
+def depth_leg(a, win, index, cn, rn, rl, dev):
+    """ONE window: plo_depth_add_dev on the window's records beside plo_records_index_dev on the same records (the same walk of every CIGAR
+    without atomics); then plo_depth_finish_dev, plo_depth_windows_dev and plo_depth_runs_dev beside a device-to-device copy of the array's
+    bytes.  The array is checked against numpy's: differences by np.add.at from every counted record's ops, depths by cumsum"""
+    import numpy as np
+    import torch
+
+    from portello_amd import abi, api, depth, devbatch
+    from portello_amd.gather import device_view
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    out = eng.liftover_batch_dev(ddesc)
+    eng.compact_output_dev(out)
+    eng.finish_batch_dev(ddesc, up.finish_in())
+    eng.sa_segments_dev(sa_in)
+    ro = eng.records_build_dev(ddesc, rin)
+    n, nb, n_ref = int(ro.n_records), int(ro.n_bytes), len(rn)
+    so = eng.records_sort_dev(ro.bytes, nb, n, ro.record_off, n_ref)  # (the index call wants them sorted; the depth does not care)
+
+    def down(ptr, count, dtype):
+        return device_view(ptr, count * np.dtype(dtype).itemsize, torch.uint8, dev).cpu().numpy().view(dtype) if count else np.zeros(0, dtype)
+
+    obj = depth.DeviceDepth(eng, rl, count_deletions=a.depth_deletions)
+    info = obj.info()
+    n_entries = int(info.n_entries)
+    slot = np.ctypeslib.as_array(info.slot_off, (n_ref + 1,)).astype(np.int64)
+    # the expected array, from the rule (records of this workload carry their CIGAR in the record: none has more than 65 535 ops)
+    data, off = down(so.bytes, nb, np.uint8), down(so.record_off, n + 1, np.uint64).astype(np.int64)
+    diff = np.zeros(n_entries, np.int64)
+    n_ops = n_counted = n_atomics = 0
+    for i in range(n):
+        p = int(off[i])
+        ref, pos = (int(x) for x in data[p + 4:p + 12].view("<i4"))
+        lrn, ncig, flag = int(data[p + 12]), int(data[p + 16:p + 18].view("<u2")[0]), int(data[p + 18:p + 20].view("<u2")[0])
+        n_ops += ncig
+        if ref < 0 or pos < 0 or flag & abi.DEPTH_EXCLUDE_DEFAULT:
+            continue
+        n_counted += 1
+        ops = data[p + 36 + lrn:p + 36 + lrn + 4 * ncig].view("<u4").astype(np.int64)
+        ln, code = ops >> 4, ops & 15
+        rlen = np.where(np.isin(code, (0, 2, 3, 7, 8)), ln, 0)
+        start = slot[ref] + pos + np.cumsum(rlen) - rlen
+        cov = (ln > 0) & (np.isin(code, (0, 7, 8)) | ((code == 2) & bool(a.depth_deletions)))
+        np.add.at(diff, start[cov], 1)
+        np.add.at(diff, (start + rlen)[cov], -1)
+        cons = cov[rlen > 0]  # the stretches: runs of covering ops among the reference-consuming ones
+        n_atomics += 2 * int((cons & ~np.concatenate([[False], cons[:-1]])).sum())
+    ao = obj.add(eng, so.bytes, nb, n, so.record_off)
+    same = int(ao.n_counted) == n_counted and np.array_equal(obj.array(eng), diff.astype(np.int32))
+    obj.finish(eng)
+    want = np.cumsum(diff)
+    same = same and np.array_equal(obj.array(eng), want.astype(np.int32))
+    first, sums, _ = obj.windows(eng, a.depth_window)
+    exp_sums = np.concatenate([np.add.reduceat(want[slot[r_]:slot[r_] + rl[r_]], np.arange(0, rl[r_], a.depth_window)) for r_ in range(n_ref) if rl[r_]] or [np.zeros(0, np.int64)])
+    same = same and np.array_equal(sums, exp_sums.astype(np.uint64))
+    runs = obj.runs(eng)
+    exp_runs = sum(1 + int((want[slot[r_] + 1:slot[r_] + rl[r_]] != want[slot[r_]:slot[r_] + rl[r_] - 1]).sum()) for r_ in range(n_ref) if rl[r_])
+    same = same and len(runs) == exp_runs and int((runs["end"] - runs["beg"]).sum()) == int(sum(rl))
+    add_ms, index_ms, finish_ms, windows_ms, runs_ms = [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        obj.reset(eng)
+        ao = obj.add(eng, so.bytes, nb, n, so.record_off)
+        io = eng.records_index_dev(so.bytes, nb, n, so.record_off, n_ref)
+        fms = obj.finish(eng)
+        _, _, wms = obj.windows(eng, a.depth_window)
+        rms = float(obj.runs_dev(eng).runs_ms)
+        if k >= a.warmup:
+            add_ms.append(float(ao.add_ms))
+            index_ms.append(float(io.index_ms))
+            finish_ms.append(fms)
+            windows_ms.append(wms)
+            runs_ms.append(rms)
+    bytes_allocated = int(obj.info().bytes_allocated)
+    obj.close()
+    src, dst = torch.zeros(max(16, 4 * n_entries), dtype=torch.uint8, device=dev), torch.empty(max(16, 4 * n_entries), dtype=torch.uint8, device=dev)
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    res = {"leg": "depth", "reads": win.n_records, "n_records": n, "n_counted": n_counted, "n_cigar_ops": n_ops, "n_atomics": n_atomics, "count_deletions": bool(a.depth_deletions),
+           "n_ref": n_ref, "array_entries": n_entries, "array_bytes": 4 * n_entries, "bytes_allocated": bytes_allocated, "window": a.depth_window, "n_windows": int(len(sums)), "n_runs": int(len(runs)),
+           "matches_numpy": bool(same), "add_ms": stats(add_ms), "index_ms_same_records": stats(index_ms), "finish_ms": stats(finish_ms), "windows_ms": stats(windows_ms),
+           "runs_ms": stats(runs_ms), "d2d_copy_of_array_ms": stats(d2d),
+           "note": "add_ms: check + add kernels (HIP events); index_ms: plo_records_index_dev, the same walk of every CIGAR without atomics; the copy moves array_bytes in and out (2 x array_bytes), the three-phase scan moves 3 x array_bytes"}
+    return res, bool(same)
+
+
 def abi_entry_dtype():
     from portello_amd import abi
 
@@ -950,6 +1054,9 @@ def main():
     ap.add_argument("--sort-out", default="", help="run the sort leg (plo_records_sort_dev on the window's records, against the host's expected order and a device-to-device copy of n_bytes) alone and write its JSON there")
     ap.add_argument("--index-out", default="", help="run the index leg (plo_records_index_dev on the window's sorted records, against the host's entries and a device-to-device copy of its algorithmic bytes; the writer's and the merge's index on the CPU) alone and write its JSON there")
     ap.add_argument("--merge-out", default="", help="run the merge leg (--merge-windows windows sorted and retained on the device; plo_runs_merge_plan_dev and the summed plo_runs_merge_emit_dev against plo_records_sort_dev over their concatenation and a device-to-device copy of the same bytes) alone and write its JSON there")
+    ap.add_argument("--depth-out", default="", help="run the depth leg (plo_depth_add_dev beside plo_records_index_dev on the same records; finish, windows and runs beside a device-to-device copy of the array) alone and write its JSON there")
+    ap.add_argument("--depth-window", type=int, default=500, help="window size of the depth leg")
+    ap.add_argument("--depth-deletions", action="store_true", help="the depth leg counts D as covered")
     ap.add_argument("--merge-windows", type=int, default=4, help="windows of the merge leg: --reads is cut into that many")
     ap.add_argument("--merge-chunk-bytes", type=int, default=1 << 30, help="chunk_bytes of the merge leg's plan")
     a = ap.parse_args()
@@ -1001,6 +1108,15 @@ def main():
             with open(a.cut_out, "w") as fh:
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
+    if a.depth_out:
+        dres, ok = depth_leg(a, win, index, cn, rn, [int(x.numel()) for x in w.chrom_seq], dev)
+        win.close()
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.depth_out)), exist_ok=True)
+        with open(a.depth_out, "w") as fh:
+            fh.write(json.dumps(dres, indent=1) + "\n")
+        print(json.dumps(dres))
         sys.exit(0 if ok else 1)
     if a.index_out:
         ires, ok = index_leg(a, win, index, cn, rn, [int(x.numel()) for x in w.chrom_seq], dev)
