@@ -1678,6 +1678,21 @@ struct HostBuf {  // pinned
     }
 };
 
+// what a count / scan / emit pass over the lifted items keeps (plo_md_dev, plo_eqx_dev; aln_pass_run)
+struct AlnPass {
+    DevBuf len, off, partial;  // [n] the items' lengths, [n + 1] their exclusive scan, the scan's block sums
+    DevBuf out;                // what the emit pass writes
+    DevBuf blk;                // err_item, the count pass's ticket, the emit pass's ticket
+    HostBuf h;                 // blk's words, and the total behind them
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    void release() {
+        for (DevBuf *b : {&len, &off, &partial, &out, &blk}) b->release();
+        h.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace
 
 struct plo_index {
@@ -1754,13 +1769,9 @@ struct plo_ctx {
     HostBuf h_nm;
     hipEvent_t nev[2] = {nullptr, nullptr};
     bool have_md = false;  // plo_md_dev's result of the current batch: plo_records_build_dev writes MD:Z from it and cuts the source's MD; dropped like have_nm
-    DevBuf md_len, md_off, md_partial, md_text, md_blk;
-    HostBuf h_md;
-    hipEvent_t mev[4] = {nullptr, nullptr, nullptr, nullptr};
+    AlnPass md;            // (out: the text)
     bool have_eqx = false;  // plo_eqx_dev's result of the current batch: plo_records_build_dev writes its = / X CIGARs in place of the lift's; dropped like have_nm
-    DevBuf eqx_len, eqx_off, eqx_partial, eqx_ops, eqx_blk;
-    HostBuf h_eqx;
-    hipEvent_t eqev[4] = {nullptr, nullptr, nullptr, nullptr};
+    AlnPass eqx;            // (out: the ops)
     // plo_records_sort_dev: buffers of its own (the sorted copy of the window's bytes, two (key, index) arrays, lengths, offsets)
     DevBuf so_key[2], so_idx[2], so_len, so_slen, so_off, so_partial, so_out, so_blk;
     HostBuf h_so;
@@ -1888,6 +1899,107 @@ static hipError_t upload(std::vector<void *> &owned, const std::vector<T> &v, co
     }
     *out = (const T *)p;
     return hipSuccess;
+}
+
+// ---- plo_nm_dev, plo_md_dev, plo_eqx_dev: the walks of aln_walk.hpp --------------------------------------------------------------
+
+// their entry: `out` cleared, the result of an earlier call dropped, and the checks they share.  fn: the function's name; bases_use: what it
+// does with the bases, for the message about their format
+template <class Out>
+static plo_status aln_enter(plo_ctx *c, const plo_batch_in *in, Out *out, bool plo_ctx::*have, const char *fn, const char *bases_use) {
+    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_item = UINT32_MAX;
+    c->err.clear();
+    c->*have = false;
+    auto fail = [&](plo_status s, const std::string &text) -> plo_status {
+        c->err = std::string(fn) + ": " + text;
+        return s;
+    };
+    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4)
+        return fail(PLO_ERR_INVALID_ARG, std::string("the batch came with sparse or ASCII bases; ") + bases_use + " complete BAM 4-bit bases (PLO_SEQ_BAM4)");
+    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads)
+        return fail(PLO_ERR_INVALID_ARG, "no lift result of this batch on the context: call plo_liftover_batch_dev on it first");
+    if (!c->have_finish) return fail(PLO_ERR_INVALID_ARG, "no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)");
+    const DevIndex &ix = c->ix->d;
+    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) return fail(PLO_ERR_INVALID_ARG, "the index has no chrom_seq");
+    if (c->last_wk.n_items > (uint32_t)NM_NO_ITEM) return fail(PLO_ERR_RANGE, "more than 2^31 - 1 items in one batch");
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    return PLO_OK;
+}
+
+// item `item` was refused by the walk; result: what is not handed out
+static plo_status aln_refused(plo_ctx *c, const char *fn, const char *result, uint32_t item, uint32_t *err_item) {
+    *err_item = item;
+    c->err = std::string(fn) + ": the CIGAR of item " + std::to_string(item) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no " + result + " is handed out";
+    return PLO_ERR_RANGE;
+}
+
+// the source fields of a DevNm, DevMd or DevEqx from the context
+static void aln_src(const plo_ctx *c, AlnSrc &s) {
+    const DevIndex &ix = c->ix->d;
+    s = AlnSrc{c->f_isoff.as<uint64_t>(), c->f_rseq.as<uint8_t>(), ix.chrom_seq, ix.chrom_len, ix.n_chroms};
+}
+
+// as many waves as stay resident (82 to 89 VGPRs: five per SIMD, five workgroups of four per CU), never more than items
+static uint32_t aln_grid(const plo_ctx *c, uint32_t n) { return std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u); }
+
+// count(nblk), the 64-bit scan of the lengths, a wait for the total and the refusal, room(total), emit(nblk), a wait behind it (the event
+// time).  Two waits.  d: DevMd or DevEqx with its source filled; count and emit launch their kernel with it, room makes room for `total`
+// and points d's emit fields at it.
+template <class D, class Count, class Room, class Emit>
+static plo_status aln_pass_run(plo_ctx *c, AlnPass &ps, D &d, const char *fn, const char *result, uint32_t *err_item, float *ms, uint64_t *total_out, Count count, Room room, Emit emit) {
+    const uint32_t n = c->last_wk.n_items;
+    hipStream_t st = c->stream;
+    for (int i = 0; i < 4; ++i)
+        if (!ps.ev[i]) HIP_TRY(c, hipEventCreate(&ps.ev[i]));
+    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
+    HIP_TRY(c, ps.len.ensure((size_t)std::max(1u, n) * 8));
+    HIP_TRY(c, ps.off.ensure(((size_t)n + 1) * 8));
+    HIP_TRY(c, ps.partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, ps.blk.ensure(16));
+    HIP_TRY(c, ps.h.ensure(32));
+    d.item_len = ps.len.as<unsigned long long>();
+    d.err_item = ps.blk.as<int>();
+    d.ticket = ps.blk.as<unsigned>() + 1;
+    unsigned long long *off = ps.off.as<unsigned long long>(), *partial = ps.partial.as<unsigned long long>();
+    uint32_t *h = ps.h.as<uint32_t>();
+    h[0] = (uint32_t)NM_NO_ITEM;
+    h[1] = h[2] = h[3] = 0;
+    h[4] = h[5] = 0;
+    HIP_TRY(c, hipMemcpyAsync(ps.blk.p, h, 16, hipMemcpyHostToDevice, st));
+    const uint32_t nblk = aln_grid(c, n);
+    HIP_TRY(c, hipEventRecord(ps.ev[0], st));
+    if (n) {
+        count(nblk);
+        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, partial);
+        hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, partial, n, nb, off);
+        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, (const unsigned long long *)partial, off);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h + 4, off + n, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(ps.off.p, 0, 8, st));
+    }
+    HIP_TRY(c, hipEventRecord(ps.ev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, ps.blk.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)NM_NO_ITEM) return aln_refused(c, fn, result, h[0], err_item);
+    const uint64_t total = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
+    HIP_TRY(c, room(total));
+    d.ticket = ps.blk.as<unsigned>() + 2;
+    HIP_TRY(c, hipEventRecord(ps.ev[2], st));
+    if (n) {
+        emit(nblk);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(ps.ev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, ps.ev[0], ps.ev[1]);
+    (void)hipEventElapsedTime(&b, ps.ev[2], ps.ev[3]);
+    *ms = a + b;
+    *total_out = total;
+    return PLO_OK;
 }
 
 extern "C" {
@@ -2417,7 +2529,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->bb_tcontig, &c->bb_tdst, &c->bb_tpos, &c->bb_tfwd, &c->bb_rev, &c->bb_len, &c->bb_soff, &c->bb_qoff, &c->bb_flags, &c->bb_sread, &c->bb_scontig,
                       &c->bb_spos, &c->bb_sfwd, &c->bb_coff, &c->bb_cigar,
                       &c->wc_guess, &c->wc_land, &c->wc_cnt, &c->wc_start, &c->wc_partial, &c->wc_fire, &c->wc_res, &c->wc_recoff, &c->wc_unmoff, &c->wc_unmsrc, &c->wc_unm, &c->ps_res,
-                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk, &c->md_len, &c->md_off, &c->md_partial, &c->md_text, &c->md_blk, &c->eqx_len, &c->eqx_off, &c->eqx_partial, &c->eqx_ops, &c->eqx_blk,
+                      &c->ci_comp, &c->ci_blk, &c->ci_st, &c->nm_out, &c->nm_blk,
                       &c->so_key[0], &c->so_key[1], &c->so_idx[0], &c->so_idx[1], &c->so_len, &c->so_slen, &c->so_off, &c->so_partial, &c->so_out, &c->so_blk, &c->bai_entry, &c->bai_blk, &c->dp_plan, &c->dp_blk,
                       &c->mg_key[0], &c->mg_key[1], &c->mg_src[0], &c->mg_src[1], &c->mg_runof, &c->mg_len, &c->mg_mlen, &c->mg_off, &c->mg_partial, &c->mg_runs, &c->mg_first, &c->mg_blk, &c->mg_cfirst,
                       &c->mg_coff, &c->mg_out, &c->mg_ooff,
@@ -2430,7 +2542,7 @@ void plo_ctx_destroy(plo_ctx *c) {
                       &c->i_item_seg, &c->i_item_cseg, &c->miss_list, &c->miss_info, &c->miss_vals, &c->miss_seq_off, &c->miss_side};
     for (DevBuf *b : bufs) b->release();
     HostBuf *hb[] = {&c->h_item_seg, &c->h_item_cseg, &c->h_status, &c->h_flip, &c->h_mapq, &c->h_chrom, &c->h_pos,
-                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_md, &c->h_eqx, &c->h_so, &c->h_bai, &c->h_dp, &c->h_mg, &c->h_mg_tab};
+                     &c->h_coff, &c->h_clen, &c->h_cigar, &c->h_counters, &c->h_miss, &c->h_side, &c->h_rec, &c->h_bgzf, &c->h_bb, &c->h_wc, &c->h_ci, &c->h_nm, &c->h_so, &c->h_bai, &c->h_dp, &c->h_mg, &c->h_mg_tab};
     for (HostBuf *b : hb) b->release();
     for (int i = 0; i < 7; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2448,10 +2560,8 @@ void plo_ctx_destroy(plo_ctx *c) {
         if (c->iev[i]) (void)hipEventDestroy(c->iev[i]);
     for (int i = 0; i < 2; ++i)
         if (c->nev[i]) (void)hipEventDestroy(c->nev[i]);
-    for (int i = 0; i < 4; ++i)
-        if (c->mev[i]) (void)hipEventDestroy(c->mev[i]);
-    for (int i = 0; i < 4; ++i)
-        if (c->eqev[i]) (void)hipEventDestroy(c->eqev[i]);
+    c->md.release();
+    c->eqx.release();
     for (int i = 0; i < 2; ++i)
         if (c->sev[i]) (void)hipEventDestroy(c->sev[i]);
     for (int i = 0; i < 2; ++i)
@@ -3725,10 +3835,10 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
     d.sa_off = c->sa_off.as<uint32_t>();
     d.sa_text = c->sa_text.as<uint8_t>();
     d.item_nm = c->have_nm ? c->nm_out.as<uint32_t>() : nullptr;
-    d.item_md_off = c->have_md ? c->md_off.as<uint64_t>() : nullptr;
-    d.md_text = c->have_md ? c->md_text.as<uint8_t>() : nullptr;
-    d.item_eqx_off = c->have_eqx ? c->eqx_off.as<uint64_t>() : nullptr;
-    d.eqx_ops = c->have_eqx ? c->eqx_ops.as<uint32_t>() : nullptr;
+    d.item_md_off = c->have_md ? c->md.off.as<uint64_t>() : nullptr;
+    d.md_text = c->have_md ? c->md.out.as<uint8_t>() : nullptr;
+    d.item_eqx_off = c->have_eqx ? c->eqx.off.as<uint64_t>() : nullptr;
+    d.eqx_ops = c->have_eqx ? c->eqx.out.as<uint32_t>() : nullptr;
     d.cs_is_fwd = c->ix->d.cs_is_fwd;
     d.contig_seg_off = c->ix->d.contig_seg_off;
     d.plan = c->r_plan.as<uint32_t>();
@@ -3796,36 +3906,9 @@ plo_status plo_records_build_dev(plo_ctx *c, const plo_batch_in *in, const plo_r
 
 // NM:i of every lifted item (nm_core.hpp): one launch of persistent waves and one wait, for the refusal, the count and the event time.
 plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
-    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    out->err_item = UINT32_MAX;
-    c->err.clear();
-    c->have_nm = false;
-    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
-        c->err = "plo_nm_dev: the batch came with sparse or ASCII bases; NM is counted over complete BAM 4-bit bases (PLO_SEQ_BAM4)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
-        c->err = "plo_nm_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_finish) {
-        c->err = "plo_nm_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevIndex &ix = c->ix->d;
-    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
-        c->err = "plo_nm_dev: the index has no chrom_seq";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevWork &wk = c->last_wk;
-    const DevBatch &bt = c->last_bt;
-    const uint32_t n = wk.n_items;
-    if (n > (uint32_t)NM_NO_ITEM) {
-        c->err = "plo_nm_dev: more than 2^31 - 1 items in one batch";
-        return PLO_ERR_RANGE;
-    }
-    HIP_TRY(c, hipSetDevice(c->ix->device));
+    const plo_status entry = aln_enter(c, in, out, &plo_ctx::have_nm, "plo_nm_dev", "NM is counted over");
+    if (entry != PLO_OK) return entry;
+    const uint32_t n = c->last_wk.n_items;
     hipStream_t st = c->stream;
     for (int i = 0; i < 2; ++i)
         if (!c->nev[i]) HIP_TRY(c, hipEventCreate(&c->nev[i]));
@@ -3834,11 +3917,7 @@ plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
     HIP_TRY(c, c->h_nm.ensure(16));
     DevNm d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = c->f_isoff.as<uint64_t>();
-    d.rev_seq = c->f_rseq.as<uint8_t>();
-    d.chrom_seq = ix.chrom_seq;
-    d.chrom_len = ix.chrom_len;
-    d.n_chroms = ix.n_chroms;
+    aln_src(c, d);
     d.item_nm = c->nm_out.as<uint32_t>();
     d.n_cmp = c->nm_blk.as<unsigned long long>();
     d.err_item = c->nm_blk.as<int>() + 2;
@@ -3849,20 +3928,14 @@ plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
     HIP_TRY(c, hipMemcpyAsync(c->nm_blk.p, h, 16, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipEventRecord(c->nev[0], st));
     if (n) {
-        // as many waves as stay resident (82 VGPRs: five per SIMD, five workgroups of four per CU), never more than items
-        const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
-        hipLaunchKernelGGL(k_nm, dim3(nblk), dim3(256), 0, st, bt, wk, d);
+        hipLaunchKernelGGL(k_nm, dim3(aln_grid(c, n)), dim3(256), 0, st, c->last_bt, c->last_wk, d);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipEventRecord(c->nev[1], st));
     HIP_TRY(c, hipMemcpyAsync(h, c->nm_blk.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     (void)hipEventElapsedTime(&out->nm_ms, c->nev[0], c->nev[1]);
-    if (h[2] != (uint32_t)NM_NO_ITEM) {
-        out->err_item = h[2];
-        c->err = "plo_nm_dev: the CIGAR of item " + std::to_string(h[2]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no NM is handed out";
-        return PLO_ERR_RANGE;
-    }
+    if (h[2] != (uint32_t)NM_NO_ITEM) return aln_refused(c, "plo_nm_dev", "NM", h[2], &out->err_item);
     out->n_items = n;
     out->item_nm = d.item_nm;
     out->n_cmp_bases = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
@@ -3870,208 +3943,54 @@ plo_status plo_nm_dev(plo_ctx *c, const plo_batch_in *in, plo_nm_out *out) {
     return PLO_OK;
 }
 
-// MD:Z of every lifted item (md_core.hpp): k_md_count, the 64-bit scan of the lengths, a wait for the total and the refusal, k_md_emit, a
-// wait behind it (the event time).  Two waits.
+// MD:Z of every lifted item (md_core.hpp): aln_pass_run with k_md_count and k_md_emit
 plo_status plo_md_dev(plo_ctx *c, const plo_batch_in *in, plo_md_out *out) {
-    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    out->err_item = UINT32_MAX;
-    c->err.clear();
-    c->have_md = false;
-    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
-        c->err = "plo_md_dev: the batch came with sparse or ASCII bases; MD is written from complete BAM 4-bit bases (PLO_SEQ_BAM4)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
-        c->err = "plo_md_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_finish) {
-        c->err = "plo_md_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevIndex &ix = c->ix->d;
-    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
-        c->err = "plo_md_dev: the index has no chrom_seq";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevWork &wk = c->last_wk;
-    const DevBatch &bt = c->last_bt;
-    const uint32_t n = wk.n_items;
-    if (n > (uint32_t)NM_NO_ITEM) {
-        c->err = "plo_md_dev: more than 2^31 - 1 items in one batch";
-        return PLO_ERR_RANGE;
-    }
-    HIP_TRY(c, hipSetDevice(c->ix->device));
+    const plo_status entry = aln_enter(c, in, out, &plo_ctx::have_md, "plo_md_dev", "MD is written from");
+    if (entry != PLO_OK) return entry;
     hipStream_t st = c->stream;
-    for (int i = 0; i < 4; ++i)
-        if (!c->mev[i]) HIP_TRY(c, hipEventCreate(&c->mev[i]));
-    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
-    HIP_TRY(c, c->md_len.ensure((size_t)std::max(1u, n) * 8));
-    HIP_TRY(c, c->md_off.ensure(((size_t)n + 1) * 8));
-    HIP_TRY(c, c->md_partial.ensure((size_t)nb * 8));
-    HIP_TRY(c, c->md_blk.ensure(16));  // err_item, the count pass's ticket, the emit pass's ticket
-    HIP_TRY(c, c->h_md.ensure(32));
     DevMd d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = c->f_isoff.as<uint64_t>();
-    d.rev_seq = c->f_rseq.as<uint8_t>();
-    d.chrom_seq = ix.chrom_seq;
-    d.chrom_len = ix.chrom_len;
-    d.n_chroms = ix.n_chroms;
-    d.item_len = c->md_len.as<unsigned long long>();
-    d.err_item = c->md_blk.as<int>();
-    d.ticket = c->md_blk.as<unsigned>() + 1;
-    unsigned long long *off = c->md_off.as<unsigned long long>();
-    uint32_t *h = c->h_md.as<uint32_t>();
-    h[0] = (uint32_t)NM_NO_ITEM;
-    h[1] = h[2] = h[3] = 0;
-    h[4] = h[5] = 0;
-    HIP_TRY(c, hipMemcpyAsync(c->md_blk.p, h, 16, hipMemcpyHostToDevice, st));
-    // as many waves as stay resident (k_nm's grid: five workgroups of four per CU at up to 96 VGPRs), never more than items
-    const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
-    HIP_TRY(c, hipEventRecord(c->mev[0], st));
-    if (n) {
-        hipLaunchKernelGGL(k_md_count, dim3(nblk), dim3(256), 0, st, bt, wk, d);
-        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, c->md_partial.as<unsigned long long>());
-        hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->md_partial.as<unsigned long long>(), n, nb, off);
-        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, (const unsigned long long *)c->md_partial.as<unsigned long long>(), off);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(h + 4, off + n, 8, hipMemcpyDeviceToHost, st));
-    } else {
-        HIP_TRY(c, hipMemsetAsync(c->md_off.p, 0, 8, st));
-    }
-    HIP_TRY(c, hipEventRecord(c->mev[1], st));
-    HIP_TRY(c, hipMemcpyAsync(h, c->md_blk.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (h[0] != (uint32_t)NM_NO_ITEM) {
-        out->err_item = h[0];
-        c->err = "plo_md_dev: the CIGAR of item " + std::to_string(h[0]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no MD is handed out";
-        return PLO_ERR_RANGE;
-    }
-    const uint64_t total = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-    HIP_TRY(c, c->md_text.ensure((size_t)total + 16));
-    d.item_md_off = off;
-    d.md_text = c->md_text.as<uint8_t>();
-    d.ticket = c->md_blk.as<unsigned>() + 2;
-    HIP_TRY(c, hipEventRecord(c->mev[2], st));
-    if (n) {
-        hipLaunchKernelGGL(k_md_emit, dim3(nblk), dim3(256), 0, st, bt, wk, d);
-        HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipEventRecord(c->mev[3], st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, c->mev[0], c->mev[1]);
-    (void)hipEventElapsedTime(&b, c->mev[2], c->mev[3]);
-    out->md_ms = a + b;
-    out->n_items = n;
-    out->item_md_off = c->md_off.as<uint64_t>();
+    aln_src(c, d);
+    const plo_status run = aln_pass_run(
+        c, c->md, d, "plo_md_dev", "MD", &out->err_item, &out->md_ms, &out->md_bytes,
+        [&](uint32_t nblk) { hipLaunchKernelGGL(k_md_count, dim3(nblk), dim3(256), 0, st, c->last_bt, c->last_wk, d); },
+        [&](uint64_t total) {
+            const hipError_t e = c->md.out.ensure((size_t)total + 16);
+            d.item_md_off = c->md.off.as<unsigned long long>();
+            d.md_text = c->md.out.as<uint8_t>();
+            return e;
+        },
+        [&](uint32_t nblk) { hipLaunchKernelGGL(k_md_emit, dim3(nblk), dim3(256), 0, st, c->last_bt, c->last_wk, d); });
+    if (run != PLO_OK) return run;
+    out->n_items = c->last_wk.n_items;
+    out->item_md_off = c->md.off.as<uint64_t>();
     out->md_text = d.md_text;
-    out->md_bytes = total;
     c->have_md = true;
     return PLO_OK;
 }
 
-// The = / X CIGAR of every lifted item (eqx_core.hpp): k_eqx_count, the 64-bit scan of the op counts, a wait for the total and the refusal,
-// k_eqx_emit, a wait behind it (the event time).  Two waits.
+// The = / X CIGAR of every lifted item (eqx_core.hpp): aln_pass_run with k_eqx_count and k_eqx_emit
 plo_status plo_eqx_dev(plo_ctx *c, const plo_batch_in *in, plo_eqx_out *out) {
-    if (!c || !in || !out) return PLO_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    out->err_item = UINT32_MAX;
-    c->err.clear();
-    c->have_eqx = false;
-    if (c->have_last && c->last_bt.seq_fmt != PLO_SEQ_BAM4) {
-        c->err = "plo_eqx_dev: the batch came with sparse or ASCII bases; the ops are written from complete BAM 4-bit bases (PLO_SEQ_BAM4)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_last || c->last_bt.n_segs != in->n_segs || c->last_bt.n_reads != in->n_reads) {
-        c->err = "plo_eqx_dev: no lift result of this batch on the context: call plo_liftover_batch_dev on it first";
-        return PLO_ERR_INVALID_ARG;
-    }
-    if (!c->have_finish) {
-        c->err = "plo_eqx_dev: no finishing result on the context: call plo_finish_batch_dev on the batch first (the reversed bases are its)";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevIndex &ix = c->ix->d;
-    if (!ix.chrom_seq || !ix.chrom_len || !ix.n_chroms) {
-        c->err = "plo_eqx_dev: the index has no chrom_seq";
-        return PLO_ERR_INVALID_ARG;
-    }
-    const DevWork &wk = c->last_wk;
-    const DevBatch &bt = c->last_bt;
-    const uint32_t n = wk.n_items;
-    if (n > (uint32_t)NM_NO_ITEM) {
-        c->err = "plo_eqx_dev: more than 2^31 - 1 items in one batch";
-        return PLO_ERR_RANGE;
-    }
-    HIP_TRY(c, hipSetDevice(c->ix->device));
+    const plo_status entry = aln_enter(c, in, out, &plo_ctx::have_eqx, "plo_eqx_dev", "the ops are written from");
+    if (entry != PLO_OK) return entry;
     hipStream_t st = c->stream;
-    for (int i = 0; i < 4; ++i)
-        if (!c->eqev[i]) HIP_TRY(c, hipEventCreate(&c->eqev[i]));
-    const uint32_t nb = std::max(1u, (n + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK);
-    HIP_TRY(c, c->eqx_len.ensure((size_t)std::max(1u, n) * 8));
-    HIP_TRY(c, c->eqx_off.ensure(((size_t)n + 1) * 8));
-    HIP_TRY(c, c->eqx_partial.ensure((size_t)nb * 8));
-    HIP_TRY(c, c->eqx_blk.ensure(16));  // err_item, the count pass's ticket, the emit pass's ticket
-    HIP_TRY(c, c->h_eqx.ensure(32));
     DevEqx d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = c->f_isoff.as<uint64_t>();
-    d.rev_seq = c->f_rseq.as<uint8_t>();
-    d.chrom_seq = ix.chrom_seq;
-    d.chrom_len = ix.chrom_len;
-    d.n_chroms = ix.n_chroms;
-    d.item_len = c->eqx_len.as<unsigned long long>();
-    d.err_item = c->eqx_blk.as<int>();
-    d.ticket = c->eqx_blk.as<unsigned>() + 1;
-    unsigned long long *off = c->eqx_off.as<unsigned long long>();
-    uint32_t *h = c->h_eqx.as<uint32_t>();
-    h[0] = (uint32_t)NM_NO_ITEM;
-    h[1] = h[2] = h[3] = 0;
-    h[4] = h[5] = 0;
-    HIP_TRY(c, hipMemcpyAsync(c->eqx_blk.p, h, 16, hipMemcpyHostToDevice, st));
-    // as many waves as stay resident (k_nm's grid: five workgroups of four per CU at up to 96 VGPRs), never more than items
-    const uint32_t nblk = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cus * 5u);
-    HIP_TRY(c, hipEventRecord(c->eqev[0], st));
-    if (n) {
-        hipLaunchKernelGGL(k_eqx_count, dim3(nblk), dim3(256), 0, st, bt, wk, d);
-        hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, c->eqx_partial.as<unsigned long long>());
-        hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, c->eqx_partial.as<unsigned long long>(), n, nb, off);
-        hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.item_len, n, nb, (const unsigned long long *)c->eqx_partial.as<unsigned long long>(), off);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(h + 4, off + n, 8, hipMemcpyDeviceToHost, st));
-    } else {
-        HIP_TRY(c, hipMemsetAsync(c->eqx_off.p, 0, 8, st));
-    }
-    HIP_TRY(c, hipEventRecord(c->eqev[1], st));
-    HIP_TRY(c, hipMemcpyAsync(h, c->eqx_blk.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (h[0] != (uint32_t)NM_NO_ITEM) {
-        out->err_item = h[0];
-        c->err = "plo_eqx_dev: the CIGAR of item " + std::to_string(h[0]) + " consumes more reference than its chromosome has behind item_ref_pos, or more bases than its read has; no CIGAR is handed out";
-        return PLO_ERR_RANGE;
-    }
-    const uint64_t total = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-    HIP_TRY(c, c->eqx_ops.ensure(((size_t)total + 4) * 4));
-    d.item_eqx_off = off;
-    d.eqx_ops = c->eqx_ops.as<uint32_t>();
-    d.ticket = c->eqx_blk.as<unsigned>() + 2;
-    HIP_TRY(c, hipEventRecord(c->eqev[2], st));
-    if (n) {
-        hipLaunchKernelGGL(k_eqx_emit, dim3(nblk), dim3(256), 0, st, bt, wk, d);
-        HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipEventRecord(c->eqev[3], st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, c->eqev[0], c->eqev[1]);
-    (void)hipEventElapsedTime(&b, c->eqev[2], c->eqev[3]);
-    out->eqx_ms = a + b;
-    out->n_items = n;
-    out->item_eqx_off = c->eqx_off.as<uint64_t>();
+    aln_src(c, d);
+    const plo_status run = aln_pass_run(
+        c, c->eqx, d, "plo_eqx_dev", "CIGAR", &out->err_item, &out->eqx_ms, &out->n_ops,
+        [&](uint32_t nblk) { hipLaunchKernelGGL(k_eqx_count, dim3(nblk), dim3(256), 0, st, c->last_bt, c->last_wk, d); },
+        [&](uint64_t total) {
+            const hipError_t e = c->eqx.out.ensure(((size_t)total + 4) * 4);
+            d.item_eqx_off = c->eqx.off.as<unsigned long long>();
+            d.eqx_ops = c->eqx.out.as<uint32_t>();
+            return e;
+        },
+        [&](uint32_t nblk) { hipLaunchKernelGGL(k_eqx_emit, dim3(nblk), dim3(256), 0, st, c->last_bt, c->last_wk, d); });
+    if (run != PLO_OK) return run;
+    out->n_items = c->last_wk.n_items;
+    out->item_eqx_off = c->eqx.off.as<uint64_t>();
     out->eqx_ops = d.eqx_ops;
-    out->n_ops = total;
     c->have_eqx = true;
     return PLO_OK;
 }

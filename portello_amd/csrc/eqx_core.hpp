@@ -6,15 +6,14 @@
 // least), so no output op is longer than the op it came from; a compared op of length 0 yields nothing.  Every other op (I, D, N, S, H, P,
 // codes 9-15) is copied as it stands, in its place.  Reference length, read length, pos, bin and the reference end do not change; the bases
 // under X plus the I and D lengths are the item's NM, the X positions the mismatch letters of its MD text that do not stand behind '^'.
-//   the shape is nm_item's and md_item's: a wave per item, the ops 64 per step, read and reference advances scanned across the wave, the
-//   same bounds check before a base of the step is touched.  Compared ops are cut into PIECES at the 16-byte lines of the reference's
-//   addresses; every other op is one piece, so the output order is the piece order.  The pieces are dealt to the lanes 64 per trip; a
-//   compared piece yields a 16-bit mismatch mask (nm_piece_t<true>).  A lane writes the runs its piece CLOSES: the run that enters the piece
-//   when its first base is of the other kind, a run for every change of kind inside it, and the run open at its end when it is its op's
-//   last piece.  Of the run that enters it a lane needs the kind (the last base of the piece in front: one shuffle, or the uniform carry
-//   for lane 0) and the length: md_seg_scan, where a piece of one kind that continues the entering run passes the length on plus its bases
-//   and any other piece restarts the sum with its trailing run.  An op's first piece always starts a run and its last piece always closes
-//   one, so nothing is open at the end of a step or of the item; the carry lives in uniform registers across the trips of a step.
+//   the walk is aln_walk.hpp's; the pieces are the 16-byte lines of the compared ops, and every other op is one piece, so the output order
+//   is the piece order.  A compared piece yields a 16-bit mismatch mask (nm_piece_t<true>).  A lane writes the runs its piece CLOSES: the
+//   run that enters the piece when its first base is of the other kind, a run for every change of kind inside it, and the run open at its
+//   end when it is its op's last piece.  Of the run that enters it a lane needs the kind (the last base of the piece in front: one shuffle,
+//   or the uniform carry for lane 0) and the length: md_seg_scan, where a piece of one kind that continues the entering run passes the
+//   length on plus its bases and any other piece restarts the sum with its trailing run.  An op's first piece always starts a run and its
+//   last piece always closes one, so nothing is open at the end of a step or of the item; the carry lives in uniform registers across the
+//   trips of a step.
 //   count and emit are one function (eqx_item<WRITE>): the count pass stores the item's op count (it needs no lengths), the 64-bit scan
 //   of records_core.hpp makes item_eqx_off, the emit pass writes the ops as 4-byte stores at item_eqx_off[i] plus a wave scan of the lanes'
 //   counts.  No LDS, no scratch.
@@ -27,13 +26,7 @@
 
 namespace plo {
 
-struct DevEqx {
-    // the context's finishing result and the index
-    const uint64_t *item_seq_off;  // PLO_NO_FLIP: the record keeps the source's bases
-    const uint8_t *rev_seq;
-    const uint8_t *const *chrom_seq;
-    const int *chrom_len;
-    uint32_t n_chroms;
+struct DevEqx : AlnSrc {
     // count pass
     unsigned long long *item_len;  // [n_items] ops of the item's = / X CIGAR (0: not LIFTED, or refused)
     int *err_item;                 // [1] the lowest item whose CIGAR leaves the chromosome or the read (NM_NO_ITEM: none)
@@ -54,38 +47,19 @@ PLO_DEV void eqx_put(const EqxSlot &o, unsigned long long at, uint32_t op) {
     if (at < o.room) o.out[at] = op;
 }
 
-PLO_DEV void eqx_refuse(const DevEqx &d, uint32_t i) {
-    if (wv::lane() == 0) {
-        wv::atomic_min(d.err_item, (int)i);
-        d.item_len[i] = 0;
-    }
-}
-
 // the = / X CIGAR of item i by one wave.  WRITE false: its op count -> item_len[i]; true: its ops -> eqx_ops + item_eqx_off[i]
 template <bool WRITE>
 PLO_DEV void eqx_item(const DevBatch &bt, const DevWork &wk, const DevEqx &d, uint32_t i) {
     const int lane = wv::lane();
-    if (wk.status[i] != PLO_ITEM_LIFTED) {  // (wave-uniform, as every branch around a wave primitive below)
+    if (!aln_lifted(wk, i)) {  // (wave-uniform, as every branch around a wave primitive below)
         if (!WRITE && lane == 0) d.item_len[i] = 0;
         return;
     }
-    const uint32_t read = bt.seg_read[wk.item_seg[i]];
-    const unsigned long long lseq = bt.read_seq_len[read];
-    const uint64_t so = d.item_seq_off[i];
-    const uint8_t *seq = so != PLO_NO_FLIP ? d.rev_seq + so : bt.seq + bt.read_seq_off[read];
-    const uintptr_t seq_lo = (uintptr_t)seq, seq_hi = seq_lo + (uintptr_t)((lseq + 1) / 2);
-    const uint32_t chrom = wk.chrom[i];
-    const long long pos = wk.pos[i];
-    const long long clen = chrom < d.n_chroms ? (long long)d.chrom_len[chrom] : -1;
-    const uint8_t *ref = chrom < d.n_chroms ? d.chrom_seq[chrom] : nullptr;
-    if (pos < 0 || pos > clen || (!ref && clen > 0)) {
-        if (!WRITE) eqx_refuse(d, i);
+    const AlnItem it = aln_open(bt, wk, d, i);
+    if (!it.ok) {
+        if (!WRITE) aln_refuse(d.err_item, d.item_len, i);
         return;
     }
-    const unsigned long long ref_room = (unsigned long long)(clen - pos);
-    const uintptr_t ref0 = (uintptr_t)ref + (uintptr_t)pos;
-    const uint32_t n = wk.cig_len[i];
-    const uint32_t *cg = wk.out_cigar + wk.cig_off[i];
     EqxSlot o = {nullptr, 0};
     if (WRITE) {
         o.out = d.eqx_ops + d.item_eqx_off[i];
@@ -93,46 +67,29 @@ PLO_DEV void eqx_item(const DevBatch &bt, const DevWork &wk, const DevEqx &d, ui
     }
     unsigned long long rd_done = 0, rf_done = 0;  // (uniform) consumed by the steps so far
     unsigned long long done = 0;                  // (uniform) ops written so far
-    for (uint32_t k = 0; k < n; k += 64) {
-        const bool has = k + (uint32_t)lane < n;
-        const uint32_t c = has ? cg[k + lane] : 0u;
-        const uint32_t t = c & 15u, len = c >> 4;
-        const bool is_cmp = has && (t == 0 || t == 7 || t == 8);
-        const unsigned long long rd_adv = has && ((0x193u >> t) & 1u) ? len : 0u;  // M I S = X
-        const unsigned long long rf_adv = has && ((0x18Du >> t) & 1u) ? len : 0u;  // M D N = X
-        const unsigned long long rd_inc = wave_scan_incl_u64(rd_adv), rf_inc = wave_scan_incl_u64(rf_adv);
-        const unsigned long long rd_end = rd_done + wv::shfl(rd_inc, 63), rf_end = rf_done + wv::shfl(rf_inc, 63);
-        if (rd_end > lseq || rf_end > ref_room) {  // the step's ops leave the read or the chromosome: none of their bases is touched
-            if (!WRITE) eqx_refuse(d, i);
+    for (uint32_t k = 0; k < it.n; k += 64) {
+        const AlnStep st = aln_step(it, k, rd_done, rf_done);
+        if (!st.ok) {
+            if (!WRITE) aln_refuse(d.err_item, d.item_len, i);
             return;
         }
-        const unsigned long long rd = rd_done + rd_inc - rd_adv;
-        const uintptr_t fa = ref0 + (uintptr_t)(rf_done + rf_inc - rf_adv);
         // a compared op: its 16-byte lines (none when it is empty); any other op: one piece, itself
-        const uint32_t np = !has ? 0u : !is_cmp ? 1u : len ? (uint32_t)(((fa + len + 15) >> 4) - (fa >> 4)) : 0u;
+        const uint32_t np = !st.has ? 0u : !st.is_cmp ? 1u : st.len ? aln_lines(st.fa, st.len) : 0u;
         const uint32_t p_inc = (uint32_t)wv::scan_add((int)np);
         const uint32_t n_pieces = (uint32_t)wv::bcast_last((int)p_inc);
         uint32_t run_c = 0, kind_c = 0;  // (uniform) the run open behind the last trip's piece 63: its length and kind
         for (uint32_t p0 = 0; p0 < n_pieces; p0 += 64) {
             const uint32_t p = p0 + (uint32_t)lane;
-            int op = 0;  // the first op with p_inc > p
-            for (int s = 32; s; s >>= 1)
-                if (wv::shfl(p_inc, op + s - 1) <= p) op += s;
-            op &= 63;
-            const uint32_t o_np = wv::shfl(np, op), o_first = wv::shfl(p_inc, op) - o_np, o_len = wv::shfl(len, op), o_c = wv::shfl(c, op);
-            const bool o_cmp = wv::shfl(is_cmp ? 1u : 0u, op) != 0;
-            const unsigned long long o_fa = wv::shfl((unsigned long long)fa, op), o_rd = wv::shfl(rd, op);
-            const bool act = p < n_pieces, cmp = act && o_cmp;
-            const uint32_t j = p - o_first;
-            const bool first = j == 0, last = j + 1 == o_np;
+            const AlnOp op = aln_find_op(st, np, p_inc, p);
+            const bool act = p < n_pieces, cmp = act && (op.t == 0 || op.t == 7 || op.t == 8);
+            const uint32_t j = p - op.first;
+            const bool first = j == 0, last = j + 1 == op.np;
             // the piece's bases and their kinds (bit k: base k mismatches)
             uint32_t nb = 0, mask = 0;
             if (cmp) {
-                uintptr_t s = ((uintptr_t)o_fa & ~(uintptr_t)15) + 16u * (uintptr_t)j, e = s + 16;
-                if (s < (uintptr_t)o_fa) s = (uintptr_t)o_fa;
-                if (e > (uintptr_t)o_fa + o_len) e = (uintptr_t)o_fa + o_len;
-                nb = (uint32_t)(e - s);
-                mask = nm_piece_t<true>(seq, seq_lo, seq_hi, (uintptr_t)o_fa, o_len, o_rd, j);
+                const AlnSpan sp = aln_span(op.fa, op.len, j);
+                nb = (uint32_t)(sp.e - sp.s);
+                mask = nm_piece_t<true>(it.seq, it.seq_lo, it.seq_hi, op.fa, op.len, op.rd, j);
             }
             const uint32_t k_first = mask & 1u, k_last = cmp ? (mask >> (nb - 1)) & 1u : 0u;
             uint32_t k_in = wv::shfl(k_last, (lane - 1) & 63);  // the kind of the run that enters the piece
@@ -154,7 +111,7 @@ PLO_DEV void eqx_item(const DevBatch &bt, const DevWork &wk, const DevEqx &d, ui
                 run_c = (end >> 32) ? (uint32_t)end : run_c + (uint32_t)end;
                 unsigned long long at = done + o_inc - n_out;
                 if (act && !cmp) {
-                    eqx_put(o, at, o_c);
+                    eqx_put(o, at, op.c);
                 } else if (cmp) {
                     uint32_t run = first ? 0u : run_in, kind = first ? k_first : k_in, from = 0, m = chg;
                     if (closes_in) {
@@ -175,22 +132,15 @@ PLO_DEV void eqx_item(const DevBatch &bt, const DevWork &wk, const DevEqx &d, ui
             }
             done += (uint32_t)wv::bcast_last((int)o_inc);
         }
-        rd_done = rd_end;
-        rf_done = rf_end;
+        rd_done = st.rd_end;
+        rf_done = st.rf_end;
     }
     if (!WRITE && lane == 0) d.item_len[i] = done;
 }
 
-// persistent waves: items by ticket
 template <bool WRITE>
 PLO_DEV void eqx_items(const DevBatch &bt, const DevWork &wk, const DevEqx &d) {
-    for (;;) {
-        unsigned i = 0;
-        if (wv::lane() == 0) i = wv::atomic_add_global(d.ticket, 1u);
-        i = wv::bcast_first(i);
-        if (i >= wk.n_items) break;
-        eqx_item<WRITE>(bt, wk, d, i);
-    }
+    aln_items(wk.n_items, d.ticket, [&](uint32_t i) { eqx_item<WRITE>(bt, wk, d, i); });
 }
 
 }  // namespace plo

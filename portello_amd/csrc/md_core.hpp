@@ -6,9 +6,8 @@
 // is never empty.  Ops of length 0 are skipped: calmd would write an empty '^' for 0D, the lift never emits one.
 // The reference letter is the chrom_seq byte: A..Z as it is, a..z upper-cased (calmd's toupper), any other byte 'N' -- the text stays
 // inside [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)* whatever the index holds.
-//   the shape is nm_item's: a wave per item, the ops 64 per step, read and reference advances scanned across the wave, the same bounds
-//   check before a base of the step is touched.  M / = / X and D ops are cut into PIECES at the 16-byte lines of the reference's addresses
-//   and dealt to the lanes 64 per trip.  A compared piece yields a 16-bit mismatch mask (nm_piece_t<true>): its events.  The matches in
+//   the walk is aln_walk.hpp's; the pieces are the 16-byte lines of the M / = / X and of the D ops.
+//   A compared piece yields a 16-bit mismatch mask (nm_piece_t<true>): its events.  The matches in
 //   front of its first event and behind its last are its leading and trailing count; a D's first piece is an event with both counts 0
 //   (it carries u and '^'), every D piece copies its letters.  A segmented scan over the lanes (a set flag cuts the sum) hands every lane
 //   the u its first event closes, a second scan over the lanes' byte counts their offsets; u and the bytes written are carried, uniform,
@@ -24,13 +23,7 @@
 
 namespace plo {
 
-struct DevMd {
-    // the context's finishing result and the index
-    const uint64_t *item_seq_off;  // PLO_NO_FLIP: the record keeps the source's bases
-    const uint8_t *rev_seq;
-    const uint8_t *const *chrom_seq;
-    const int *chrom_len;
-    uint32_t n_chroms;
+struct DevMd : AlnSrc {
     // count pass
     unsigned long long *item_len;  // [n_items] bytes of the item's text (0: not LIFTED, or refused)
     int *err_item;                 // [1] the lowest item whose CIGAR leaves the chromosome or the read (NM_NO_ITEM: none)
@@ -94,38 +87,19 @@ PLO_DEV unsigned long long md_seg_scan(unsigned long long x) {
     return x;
 }
 
-PLO_DEV void md_refuse(const DevMd &d, uint32_t i) {
-    if (wv::lane() == 0) {
-        wv::atomic_min(d.err_item, (int)i);
-        d.item_len[i] = 0;
-    }
-}
-
 // the text of item i by one wave.  WRITE false: its length -> item_len[i]; true: its bytes -> md_text + item_md_off[i]
 template <bool WRITE>
 PLO_DEV void md_item(const DevBatch &bt, const DevWork &wk, const DevMd &d, uint32_t i) {
     const int lane = wv::lane();
-    if (wk.status[i] != PLO_ITEM_LIFTED) {  // (wave-uniform, as every branch around a wave primitive below)
+    if (!aln_lifted(wk, i)) {  // (wave-uniform, as every branch around a wave primitive below)
         if (!WRITE && lane == 0) d.item_len[i] = 0;
         return;
     }
-    const uint32_t read = bt.seg_read[wk.item_seg[i]];
-    const unsigned long long lseq = bt.read_seq_len[read];
-    const uint64_t so = d.item_seq_off[i];
-    const uint8_t *seq = so != PLO_NO_FLIP ? d.rev_seq + so : bt.seq + bt.read_seq_off[read];
-    const uintptr_t seq_lo = (uintptr_t)seq, seq_hi = seq_lo + (uintptr_t)((lseq + 1) / 2);
-    const uint32_t chrom = wk.chrom[i];
-    const long long pos = wk.pos[i];
-    const long long clen = chrom < d.n_chroms ? (long long)d.chrom_len[chrom] : -1;
-    const uint8_t *ref = chrom < d.n_chroms ? d.chrom_seq[chrom] : nullptr;
-    if (pos < 0 || pos > clen || (!ref && clen > 0)) {
-        if (!WRITE) md_refuse(d, i);
+    const AlnItem it = aln_open(bt, wk, d, i);
+    if (!it.ok) {
+        if (!WRITE) aln_refuse(d.err_item, d.item_len, i);
         return;
     }
-    const unsigned long long ref_room = (unsigned long long)(clen - pos);
-    const uintptr_t ref0 = (uintptr_t)ref + (uintptr_t)pos;
-    const uint32_t n = wk.cig_len[i];
-    const uint32_t *cg = wk.out_cigar + wk.cig_off[i];
     MdSlot o = {nullptr, 0};
     if (WRITE) {
         o.out = d.md_text + d.item_md_off[i];
@@ -134,43 +108,27 @@ PLO_DEV void md_item(const DevBatch &bt, const DevWork &wk, const DevMd &d, uint
     unsigned long long rd_done = 0, rf_done = 0;  // (uniform) consumed by the steps so far
     uint32_t u = 0;                               // (uniform) the matches open behind the last event
     unsigned long long done = 0;                  // (uniform) bytes of the text so far
-    for (uint32_t k = 0; k < n; k += 64) {
-        const bool has = k + (uint32_t)lane < n;
-        const uint32_t c = has ? cg[k + lane] : 0u;
-        const uint32_t t = c & 15u, len = c >> 4;
-        const bool is_cmp = has && (t == 0 || t == 7 || t == 8), is_del = has && t == 2;
-        const unsigned long long rd_adv = has && ((0x193u >> t) & 1u) ? len : 0u;  // M I S = X
-        const unsigned long long rf_adv = has && ((0x18Du >> t) & 1u) ? len : 0u;  // M D N = X
-        const unsigned long long rd_inc = wave_scan_incl_u64(rd_adv), rf_inc = wave_scan_incl_u64(rf_adv);
-        const unsigned long long rd_end = rd_done + wv::shfl(rd_inc, 63), rf_end = rf_done + wv::shfl(rf_inc, 63);
-        if (rd_end > lseq || rf_end > ref_room) {  // the step's ops leave the read or the chromosome: none of their bases is touched
-            if (!WRITE) md_refuse(d, i);
+    for (uint32_t k = 0; k < it.n; k += 64) {
+        const AlnStep st = aln_step(it, k, rd_done, rf_done);
+        if (!st.ok) {
+            if (!WRITE) aln_refuse(d.err_item, d.item_len, i);
             return;
         }
-        const unsigned long long rd = rd_done + rd_inc - rd_adv;
-        const uintptr_t fa = ref0 + (uintptr_t)(rf_done + rf_inc - rf_adv);
-        const uint32_t np = (is_cmp || is_del) && len ? (uint32_t)(((fa + len + 15) >> 4) - (fa >> 4)) : 0u;
+        const bool is_del = st.has && st.t == 2;
+        const uint32_t np = (st.is_cmp || is_del) && st.len ? aln_lines(st.fa, st.len) : 0u;
         const uint32_t p_inc = (uint32_t)wv::scan_add((int)np);
         const uint32_t n_pieces = (uint32_t)wv::bcast_last((int)p_inc);
         for (uint32_t p0 = 0; p0 < n_pieces; p0 += 64) {
             const uint32_t p = p0 + (uint32_t)lane;
-            int op = 0;  // the first op with p_inc > p
-            for (int s = 32; s; s >>= 1)
-                if (wv::shfl(p_inc, op + s - 1) <= p) op += s;
-            op &= 63;
-            const uint32_t o_first = wv::shfl(p_inc, op) - wv::shfl(np, op), o_len = wv::shfl(len, op);
-            const bool o_del = wv::shfl(is_del ? 1u : 0u, op) != 0;
-            const unsigned long long o_fa = wv::shfl((unsigned long long)fa, op), o_rd = wv::shfl(rd, op);
+            const AlnOp op = aln_find_op(st, np, p_inc, p);
+            const bool o_del = op.t == 2;
             const bool act = p < n_pieces;
-            const uint32_t j = p - o_first;
-            // the piece's reference bytes [s, e)
-            uintptr_t s = ((uintptr_t)o_fa & ~(uintptr_t)15) + 16u * (uintptr_t)j, e = s + 16;
-            if (s < (uintptr_t)o_fa) s = (uintptr_t)o_fa;
-            if (e > (uintptr_t)o_fa + o_len) e = (uintptr_t)o_fa + o_len;
-            const uint32_t nb_ref = act ? (uint32_t)(e - s) : 0u;
-            const uint8_t *rf = (const uint8_t *)s;
+            const uint32_t j = p - op.first;
+            const AlnSpan sp = aln_span(op.fa, op.len, j);  // the piece's reference bytes
+            const uint32_t nb_ref = act ? (uint32_t)(sp.e - sp.s) : 0u;
+            const uint8_t *rf = (const uint8_t *)sp.s;
             uint32_t mask = 0;
-            if (act && !o_del) mask = nm_piece_t<true>(seq, seq_lo, seq_hi, (uintptr_t)o_fa, o_len, o_rd, j);
+            if (act && !o_del) mask = nm_piece_t<true>(it.seq, it.seq_lo, it.seq_hi, op.fa, op.len, op.rd, j);
             const bool ev = act && (o_del || mask != 0);
             const uint32_t lead = !act || o_del ? 0u : mask ? (uint32_t)wv::ctz32(mask) : nb_ref;
             const uint32_t trail = mask ? nb_ref - 1u - (31u - (uint32_t)wv::clz32(mask)) : 0u;
@@ -201,8 +159,8 @@ PLO_DEV void md_item(const DevBatch &bt, const DevWork &wk, const DevMd &d, uint
             }
             done += (uint32_t)wv::bcast_last((int)b_inc);
         }
-        rd_done = rd_end;
-        rf_done = rf_end;
+        rd_done = st.rd_end;
+        rf_done = st.rf_end;
     }
     if (lane == 0) {
         if (WRITE) md_put_dec(o, done, u);
@@ -210,16 +168,9 @@ PLO_DEV void md_item(const DevBatch &bt, const DevWork &wk, const DevMd &d, uint
     }
 }
 
-// persistent waves: items by ticket
 template <bool WRITE>
 PLO_DEV void md_items(const DevBatch &bt, const DevWork &wk, const DevMd &d) {
-    for (;;) {
-        unsigned i = 0;
-        if (wv::lane() == 0) i = wv::atomic_add_global(d.ticket, 1u);
-        i = wv::bcast_first(i);
-        if (i >= wk.n_items) break;
-        md_item<WRITE>(bt, wk, d, i);
-    }
+    aln_items(wk.n_items, d.ticket, [&](uint32_t i) { md_item<WRITE>(bt, wk, d, i); });
 }
 
 }  // namespace plo

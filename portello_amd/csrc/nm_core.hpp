@@ -5,10 +5,7 @@
 // its length and advances the reference, N advances the reference, S the read, H and P do nothing.
 // Since the table is one-to-one, "c1 == c2 and c1 != 15" is "the reference byte is table[c1]" for c1 in 1..14: the read's codes are
 // turned into the characters they stand for (two v_perm_b32 per four bases) and compared with the reference bytes as they lie.
-//   a wave per item: the ops 64 per step, one per lane; their read and reference advances are scanned across the wave (the bounds check
-//   of the step comes out of the same scans, before a base of the step is touched).  Every M / = / X op is cut into PIECES at the 16-byte
-//   lines of the reference's ADDRESSES, the pieces of the step's ops are counted by a third scan and dealt to the lanes 64 per trip (a lane
-//   finds its op by a search over that scan: six shuffles).  64 matches of a few bases are one trip, a match of 15 kb is fifteen.
+//   the walk is aln_walk.hpp's; a piece is one 16-byte line of an M / = / X op, and the pair rule on a piece is this file's (nm_piece_t):
 //   a whole piece: 16 aligned bytes of the reference, two aligned 8-byte loads of the read's nibbles (realigned by a funnel shift
 //   of whole bytes; an odd read position takes the low nibbles first), sixteen bases compared in four dwords.
 //   a part piece (head and tail of an op, any op below 16 bases), and a whole one whose 8-byte words would reach outside the read's
@@ -18,19 +15,11 @@
 #include <plo_wave.hpp>
 #include <stdint.h>
 
-#include "records_core.hpp"
+#include "aln_walk.hpp"
 
 namespace plo {
 
-constexpr int NM_NO_ITEM = 0x7fffffff;
-
-struct DevNm {
-    // the context's finishing result and the index
-    const uint64_t *item_seq_off;  // PLO_NO_FLIP: the record keeps the source's bases
-    const uint8_t *rev_seq;
-    const uint8_t *const *chrom_seq;
-    const int *chrom_len;
-    uint32_t n_chroms;
+struct DevNm : AlnSrc {
     // output
     uint32_t *item_nm;              // [n_items]
     unsigned long long *n_cmp;      // [1] bases compared, whole batch
@@ -67,9 +56,8 @@ PLO_DEV uint32_t nm_mismatch1(unsigned c1, unsigned ch) {
 // [seq_lo, seq_hi) their addresses.  MASK false: the piece's mismatches (k_nm); true: bit k set where its base k mismatches (md_core.hpp)
 template <bool MASK>
 PLO_DEV uint32_t nm_piece_t(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi, uintptr_t fa, uint32_t len, unsigned long long rd, uint32_t j) {
-    uintptr_t s = (fa & ~(uintptr_t)15) + 16u * (uintptr_t)j, e = s + 16;
-    if (s < fa) s = fa;
-    if (e > fa + len) e = fa + len;
+    const AlnSpan sp = aln_span(fa, len, j);
+    const uintptr_t s = sp.s, e = sp.e;
     const unsigned long long rp = rd + (unsigned long long)(s - fa);
     if (e - s == 16) {
         const uintptr_t b = seq_lo + (uintptr_t)(rp >> 1), w = b & ~(uintptr_t)7;
@@ -107,86 +95,40 @@ PLO_DEV uint32_t nm_piece(const uint8_t *seq, uintptr_t seq_lo, uintptr_t seq_hi
     return nm_piece_t<false>(seq, seq_lo, seq_hi, fa, len, rd, j);
 }
 
-PLO_DEV void nm_refuse(const DevNm &d, uint32_t i) {
-    if (wv::lane() == 0) {
-        wv::atomic_min(d.err_item, (int)i);
-        d.item_nm[i] = 0;
-    }
-}
-
 // NM of item i by one wave; cmp (per lane) gathers the bases compared
 PLO_DEV void nm_item(const DevBatch &bt, const DevWork &wk, const DevNm &d, uint32_t i, unsigned long long &cmp) {
     const int lane = wv::lane();
-    if (wk.status[i] != PLO_ITEM_LIFTED) {  // (wave-uniform, as every branch around a wave primitive below)
+    if (!aln_lifted(wk, i)) {  // (wave-uniform, as every branch around a wave primitive below)
         if (lane == 0) d.item_nm[i] = 0;
         return;
     }
-    const uint32_t read = bt.seg_read[wk.item_seg[i]];
-    const unsigned long long lseq = bt.read_seq_len[read];
-    const uint64_t so = d.item_seq_off[i];
-    const uint8_t *seq = so != PLO_NO_FLIP ? d.rev_seq + so : bt.seq + bt.read_seq_off[read];
-    const uintptr_t seq_lo = (uintptr_t)seq, seq_hi = seq_lo + (uintptr_t)((lseq + 1) / 2);
-    const uint32_t chrom = wk.chrom[i];
-    const long long pos = wk.pos[i];
-    const long long clen = chrom < d.n_chroms ? (long long)d.chrom_len[chrom] : -1;
-    const uint8_t *ref = chrom < d.n_chroms ? d.chrom_seq[chrom] : nullptr;
-    if (pos < 0 || pos > clen || (!ref && clen > 0)) {
-        nm_refuse(d, i);
-        return;
-    }
-    const unsigned long long ref_room = (unsigned long long)(clen - pos);
-    const uintptr_t ref0 = (uintptr_t)ref + (uintptr_t)pos;
-    const uint32_t n = wk.cig_len[i];
-    const uint32_t *cg = wk.out_cigar + wk.cig_off[i];
+    const AlnItem it = aln_open(bt, wk, d, i);
+    if (!it.ok) return aln_refuse(d.err_item, d.item_nm, i);
     unsigned long long rd_done = 0, rf_done = 0;  // (uniform) consumed by the steps so far
     uint32_t nm = 0;                              // (per lane)
-    for (uint32_t k = 0; k < n; k += 64) {
-        const bool has = k + (uint32_t)lane < n;
-        const uint32_t c = has ? cg[k + lane] : 0u;
-        const uint32_t t = c & 15u, len = c >> 4;
-        const bool is_cmp = has && (t == 0 || t == 7 || t == 8);
-        const unsigned long long rd_adv = has && ((0x193u >> t) & 1u) ? len : 0u;  // M I S = X
-        const unsigned long long rf_adv = has && ((0x18Du >> t) & 1u) ? len : 0u;  // M D N = X
-        if (has && (t == 1 || t == 2)) nm += len;
-        const unsigned long long rd_inc = wave_scan_incl_u64(rd_adv), rf_inc = wave_scan_incl_u64(rf_adv);
-        const unsigned long long rd_end = rd_done + wv::shfl(rd_inc, 63), rf_end = rf_done + wv::shfl(rf_inc, 63);
-        if (rd_end > lseq || rf_end > ref_room) {  // the step's ops leave the read or the chromosome: none of their bases is touched
-            nm_refuse(d, i);
-            return;
-        }
-        const unsigned long long rd = rd_done + rd_inc - rd_adv;
-        const uintptr_t fa = ref0 + (uintptr_t)(rf_done + rf_inc - rf_adv);
-        const uint32_t np = is_cmp && len ? (uint32_t)(((fa + len + 15) >> 4) - (fa >> 4)) : 0u;
+    for (uint32_t k = 0; k < it.n; k += 64) {
+        const AlnStep st = aln_step(it, k, rd_done, rf_done);
+        if (!st.ok) return aln_refuse(d.err_item, d.item_nm, i);
+        if (st.has && (st.t == 1 || st.t == 2)) nm += st.len;
+        const uint32_t np = st.is_cmp && st.len ? aln_lines(st.fa, st.len) : 0u;
         const uint32_t p_inc = (uint32_t)wv::scan_add((int)np);
         const uint32_t n_pieces = (uint32_t)wv::bcast_last((int)p_inc);
-        if (is_cmp) cmp += len;
+        if (st.is_cmp) cmp += st.len;
         for (uint32_t p0 = 0; p0 < n_pieces; p0 += 64) {
             const uint32_t p = p0 + (uint32_t)lane;
-            int o = 0;  // the first op with p_inc > p
-            for (int s = 32; s; s >>= 1)
-                if (wv::shfl(p_inc, o + s - 1) <= p) o += s;
-            o &= 63;
-            const uint32_t o_first = wv::shfl(p_inc, o) - wv::shfl(np, o), o_len = wv::shfl(len, o);
-            const unsigned long long o_fa = wv::shfl((unsigned long long)fa, o), o_rd = wv::shfl(rd, o);
-            if (p < n_pieces) nm += nm_piece(seq, seq_lo, seq_hi, (uintptr_t)o_fa, o_len, o_rd, p - o_first);
+            const AlnOp o = aln_find_op(st, np, p_inc, p);
+            if (p < n_pieces) nm += nm_piece(it.seq, it.seq_lo, it.seq_hi, o.fa, o.len, o.rd, p - o.first);
         }
-        rd_done = rd_end;
-        rf_done = rf_end;
+        rd_done = st.rd_end;
+        rf_done = st.rf_end;
     }
     const uint32_t total = (uint32_t)wv::reduce_add((int)nm);
     if (lane == 0) d.item_nm[i] = total;
 }
 
-// persistent waves: items by ticket
 PLO_DEV void nm_items(const DevBatch &bt, const DevWork &wk, const DevNm &d) {
     unsigned long long cmp = 0;
-    for (;;) {
-        unsigned i = 0;
-        if (wv::lane() == 0) i = wv::atomic_add_global(d.ticket, 1u);
-        i = wv::bcast_first(i);
-        if (i >= wk.n_items) break;
-        nm_item(bt, wk, d, i, cmp);
-    }
+    aln_items(wk.n_items, d.ticket, [&](uint32_t i) { nm_item(bt, wk, d, i, cmp); });
     cmp = wv::shfl(wave_scan_incl_u64(cmp), 63);
     if (wv::lane() == 0 && cmp) wv::atomic_add_global(d.n_cmp, cmp);
 }

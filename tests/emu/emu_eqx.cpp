@@ -11,22 +11,12 @@
 namespace {
 constexpr uint32_t EQX_CANARY = 0xA5A5A5A5u;  // no op of a test's CIGAR (an H of 2^28 - 1 bases and change)
 
-// one pass over the items: item_seed 0 = the ticket loop of eqx_items in one wave, otherwise eqx_item per item in shuffled order
 template <bool WRITE>
 void run_eqx_pass(const DevBatch &bt, const DevWork &wk, DevEqx d, unsigned order_seed, unsigned item_seed) {
     unsigned ticket = 0;
     d.ticket = &ticket;
-    if (!item_seed) {
-        wv::EmuWave ew;
-        ew.order_seed = order_seed;
-        ew.run([&]() { eqx_items<WRITE>(bt, wk, d); });
-        return;
-    }
-    for (uint32_t i : item_order(wk.n_items, item_seed)) {
-        wv::EmuWave ew;
-        ew.order_seed = order_seed;
-        ew.run([&]() { eqx_item<WRITE>(bt, wk, d, i); });
-    }
+    run_pass(
+        wk.n_items, order_seed, item_seed, [&]() { eqx_items<WRITE>(bt, wk, d); }, [&](uint32_t i) { eqx_item<WRITE>(bt, wk, d, i); });
 }
 
 struct EqxResult {
@@ -76,25 +66,17 @@ EqxResult *g_eqx = nullptr;
 // -2 / -3 when the emit stored outside the ops / left one of them unwritten.  The ops stay with the library: emu_eqx_ops copies them.
 extern "C" int emu_eqx_batch(const plo_batch_in *in, const plo_batch_out *lift, const uint64_t *item_seq_off, const uint8_t *rev_seq, const plo_index_desc *ix,
                              unsigned order_seed, unsigned item_seed, uint64_t *item_eqx_off, uint64_t *item_len, uint32_t *err_item) {
-    DevBatch bt;
-    DevWork wk;
-    fill_work(bt, wk, in, lift);
-    std::vector<int> clen(ix->n_chroms ? ix->n_chroms : 1, 0);
-    for (uint32_t c = 0; c < ix->n_chroms; ++c) clen[c] = (int)ix->chrom_len[c];
+    const BatchWalk b(in, lift, item_seq_off, rev_seq, ix);
     DevEqx d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = item_seq_off;
-    d.rev_seq = rev_seq;
-    d.chrom_seq = ix->chrom_seq;
-    d.chrom_len = clen.data();
-    d.n_chroms = ix->n_chroms;
+    static_cast<AlnSrc &>(d) = b.src;
     delete g_eqx;
     g_eqx = new EqxResult();
-    run_eqx(bt, wk, d, order_seed, item_seed, 16, *g_eqx);
+    run_eqx(b.bt, b.wk, d, order_seed, item_seed, 16, *g_eqx);
     *err_item = g_eqx->err_item;
     if (g_eqx->status != PLO_OK) return g_eqx->status;
-    for (uint32_t i = 0; i <= wk.n_items; ++i) item_eqx_off[i] = g_eqx->off[i];
-    for (uint32_t i = 0; i < wk.n_items; ++i) item_len[i] = g_eqx->len[i];
+    for (uint32_t i = 0; i <= b.wk.n_items; ++i) item_eqx_off[i] = g_eqx->off[i];
+    for (uint32_t i = 0; i < b.wk.n_items; ++i) item_len[i] = g_eqx->len[i];
     return g_eqx->check ? -g_eqx->check : PLO_OK;
 }
 extern "C" void emu_eqx_ops(uint32_t *dst) {
@@ -109,36 +91,11 @@ namespace {
 // one item on its own, as md_one
 void eqx_one(const uint32_t *ops, uint32_t n_ops, const uint8_t *seq, uint32_t l_seq, int flip, const uint8_t *ref, int chrom_len, int64_t ref_pos, unsigned order_seed,
              size_t guard, EqxResult &r) {
-    const uint32_t zero = 0;
-    const uint64_t off0 = 0, seq_off = flip ? 0 : PLO_NO_FLIP;
-    const uint8_t lifted = PLO_ITEM_LIFTED;
-    DevBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    bt.read_seq_len = &l_seq;
-    bt.read_seq_off = &off0;
-    bt.seq = flip ? nullptr : seq;
-    bt.seq_bytes = flip ? 0 : (l_seq + 1) / 2;
-    bt.seg_read = &zero;
-    bt.seq_fmt = PLO_SEQ_BAM4;
-    bt.n_reads = bt.n_segs = 1;
-    DevWork wk;
-    memset(&wk, 0, sizeof(wk));
-    wk.n_items = 1;
-    wk.item_seg = (uint32_t *)&zero;
-    wk.status = (uint8_t *)&lifted;
-    wk.chrom = (uint32_t *)&zero;
-    wk.pos = &ref_pos;
-    wk.cig_off = (uint64_t *)&off0;
-    wk.cig_len = &n_ops;
-    wk.out_cigar = (uint32_t *)ops;
+    const OneWalk w(ops, n_ops, seq, l_seq, flip, ref, chrom_len, ref_pos);
     DevEqx d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = &seq_off;
-    d.rev_seq = flip ? seq : nullptr;
-    d.chrom_seq = &ref;
-    d.chrom_len = &chrom_len;
-    d.n_chroms = 1;
-    run_eqx(bt, wk, d, order_seed, order_seed ? 1u : 0u, guard, r);
+    static_cast<AlnSrc &>(d) = w.src;
+    run_eqx(w.bt, w.wk, d, order_seed, order_seed ? 1u : 0u, guard, r);
 }
 }  // namespace
 

@@ -11,33 +11,12 @@
 namespace {
 constexpr uint8_t MD_CANARY = 0xA5;  // no byte of an MD text
 
-std::vector<uint32_t> item_order(uint32_t n, unsigned item_seed) {
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    unsigned rs = item_seed;
-    for (uint32_t i = n; i > 1; --i) {
-        rs = rs * 1664525u + 1013904223u;
-        std::swap(order[i - 1], order[(rs >> 8) % i]);
-    }
-    return order;
-}
-
-// one pass over the items: item_seed 0 = the ticket loop of md_items in one wave, otherwise md_item per item in shuffled order
 template <bool WRITE>
 void run_md_pass(const DevBatch &bt, const DevWork &wk, DevMd d, unsigned order_seed, unsigned item_seed) {
     unsigned ticket = 0;
     d.ticket = &ticket;
-    if (!item_seed) {
-        wv::EmuWave ew;
-        ew.order_seed = order_seed;
-        ew.run([&]() { md_items<WRITE>(bt, wk, d); });
-        return;
-    }
-    for (uint32_t i : item_order(wk.n_items, item_seed)) {
-        wv::EmuWave ew;
-        ew.order_seed = order_seed;
-        ew.run([&]() { md_item<WRITE>(bt, wk, d, i); });
-    }
+    run_pass(
+        wk.n_items, order_seed, item_seed, [&]() { md_items<WRITE>(bt, wk, d); }, [&](uint32_t i) { md_item<WRITE>(bt, wk, d, i); });
 }
 
 struct MdResult {
@@ -87,25 +66,17 @@ MdResult *g_md = nullptr;
 // -2 / -3 when the emit stored outside the text / left a byte of it unwritten.  The text stays with the library: emu_md_text copies it.
 extern "C" int emu_md_batch(const plo_batch_in *in, const plo_batch_out *lift, const uint64_t *item_seq_off, const uint8_t *rev_seq, const plo_index_desc *ix,
                             unsigned order_seed, unsigned item_seed, uint64_t *item_md_off, uint64_t *item_len, uint32_t *err_item) {
-    DevBatch bt;
-    DevWork wk;
-    fill_work(bt, wk, in, lift);
-    std::vector<int> clen(ix->n_chroms ? ix->n_chroms : 1, 0);
-    for (uint32_t c = 0; c < ix->n_chroms; ++c) clen[c] = (int)ix->chrom_len[c];
+    const BatchWalk b(in, lift, item_seq_off, rev_seq, ix);
     DevMd d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = item_seq_off;
-    d.rev_seq = rev_seq;
-    d.chrom_seq = ix->chrom_seq;
-    d.chrom_len = clen.data();
-    d.n_chroms = ix->n_chroms;
+    static_cast<AlnSrc &>(d) = b.src;
     delete g_md;
     g_md = new MdResult();
-    run_md(bt, wk, d, order_seed, item_seed, 64, *g_md);
+    run_md(b.bt, b.wk, d, order_seed, item_seed, 64, *g_md);
     *err_item = g_md->err_item;
     if (g_md->status != PLO_OK) return g_md->status;
-    for (uint32_t i = 0; i <= wk.n_items; ++i) item_md_off[i] = g_md->off[i];
-    for (uint32_t i = 0; i < wk.n_items; ++i) item_len[i] = g_md->len[i];
+    for (uint32_t i = 0; i <= b.wk.n_items; ++i) item_md_off[i] = g_md->off[i];
+    for (uint32_t i = 0; i < b.wk.n_items; ++i) item_len[i] = g_md->len[i];
     return g_md->check ? -g_md->check : PLO_OK;
 }
 extern "C" void emu_md_text(uint8_t *dst) {
@@ -120,36 +91,11 @@ namespace {
 // one item on its own, as emu_nm_one
 void md_one(const uint32_t *ops, uint32_t n_ops, const uint8_t *seq, uint32_t l_seq, int flip, const uint8_t *ref, int chrom_len, int64_t ref_pos, unsigned order_seed,
             size_t guard, MdResult &r) {
-    const uint32_t zero = 0;
-    const uint64_t off0 = 0, seq_off = flip ? 0 : PLO_NO_FLIP;
-    const uint8_t lifted = PLO_ITEM_LIFTED;
-    DevBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    bt.read_seq_len = &l_seq;
-    bt.read_seq_off = &off0;
-    bt.seq = flip ? nullptr : seq;
-    bt.seq_bytes = flip ? 0 : (l_seq + 1) / 2;
-    bt.seg_read = &zero;
-    bt.seq_fmt = PLO_SEQ_BAM4;
-    bt.n_reads = bt.n_segs = 1;
-    DevWork wk;
-    memset(&wk, 0, sizeof(wk));
-    wk.n_items = 1;
-    wk.item_seg = (uint32_t *)&zero;
-    wk.status = (uint8_t *)&lifted;
-    wk.chrom = (uint32_t *)&zero;
-    wk.pos = &ref_pos;
-    wk.cig_off = (uint64_t *)&off0;
-    wk.cig_len = &n_ops;
-    wk.out_cigar = (uint32_t *)ops;
+    const OneWalk w(ops, n_ops, seq, l_seq, flip, ref, chrom_len, ref_pos);
     DevMd d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = &seq_off;
-    d.rev_seq = flip ? seq : nullptr;
-    d.chrom_seq = &ref;
-    d.chrom_len = &chrom_len;
-    d.n_chroms = 1;
-    run_md(bt, wk, d, order_seed, order_seed ? 1u : 0u, guard, r);
+    static_cast<AlnSrc &>(d) = w.src;
+    run_md(w.bt, w.wk, d, order_seed, order_seed ? 1u : 0u, guard, r);
 }
 }  // namespace
 

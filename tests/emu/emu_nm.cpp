@@ -8,38 +8,45 @@
 #include "../../portello_amd/csrc/nm_core.hpp"
 
 namespace {
-// item order of a run: item_seed 0 = the ticket loop of nm_items in one wave, otherwise nm_item per item in shuffled order
+// one pass over the items (emu_md.cpp and emu_eqx.cpp run theirs through it too): item_seed 0 = the ticket loop `items` in one wave,
+// otherwise `item(i)` for every item in shuffled order, a wave each
+template <class Items, class Item>
+void run_pass(uint32_t n, unsigned order_seed, unsigned item_seed, Items items, Item item) {
+    if (!item_seed) {
+        wv::EmuWave ew;
+        ew.order_seed = order_seed;
+        ew.run(items);
+        return;
+    }
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    unsigned rs = item_seed;
+    for (uint32_t i = n; i > 1; --i) {
+        rs = rs * 1664525u + 1013904223u;
+        std::swap(order[i - 1], order[(rs >> 8) % i]);
+    }
+    for (uint32_t i : order) {
+        wv::EmuWave ew;
+        ew.order_seed = order_seed;
+        ew.run([&]() { item(i); });
+    }
+}
+
 int run_nm(const DevBatch &bt, const DevWork &wk, DevNm d, unsigned order_seed, unsigned item_seed, uint64_t *n_cmp, uint32_t *err_item) {
-    unsigned long long cmp_total = 0;
+    unsigned long long cmp_total = 0, lane_cmp[64] = {0};
     int err = NM_NO_ITEM;
     unsigned ticket = 0;
     d.n_cmp = &cmp_total;
     d.err_item = &err;
     d.ticket = &ticket;
-    if (!item_seed) {
-        wv::EmuWave ew;
-        ew.order_seed = order_seed;
-        ew.run([&]() { nm_items(bt, wk, d); });
-    } else {
-        std::vector<uint32_t> order(wk.n_items);
-        for (uint32_t i = 0; i < wk.n_items; ++i) order[i] = i;
-        unsigned rs = item_seed;
-        for (uint32_t i = wk.n_items; i > 1; --i) {
-            rs = rs * 1664525u + 1013904223u;
-            std::swap(order[i - 1], order[(rs >> 8) % i]);
-        }
-        for (uint32_t i : order) {
-            unsigned long long lane_cmp[64] = {0};
-            wv::EmuWave ew;
-            ew.order_seed = order_seed;
-            ew.run([&]() {
-                unsigned long long c = 0;
-                nm_item(bt, wk, d, i, c);
-                lane_cmp[wv::lane()] = c;
-            });
-            for (int l = 0; l < 64; ++l) cmp_total += lane_cmp[l];
-        }
-    }
+    run_pass(
+        wk.n_items, order_seed, item_seed, [&]() { nm_items(bt, wk, d); },
+        [&](uint32_t i) {
+            unsigned long long c = 0;
+            nm_item(bt, wk, d, i, c);
+            lane_cmp[wv::lane()] += c;
+        });
+    for (int l = 0; l < 64; ++l) cmp_total += lane_cmp[l];
     *n_cmp = cmp_total;
     *err_item = err == NM_NO_ITEM ? UINT32_MAX : (uint32_t)err;
     return err == NM_NO_ITEM ? PLO_OK : PLO_ERR_RANGE;
@@ -68,64 +75,94 @@ void fill_work(DevBatch &bt, DevWork &wk, const plo_batch_in *in, const plo_batc
     wk.cig_len = (uint32_t *)lift->item_cigar_len;
     wk.out_cigar = (uint32_t *)lift->cigar;
 }
-}  // namespace
 
-// a whole batch: `lift` = host arrays of a lift result, item_seq_off / rev_seq = emu_finish_batch's, `ix` = the index description (its
-// chromosomes).  item_nm: [n_items].  Returns PLO_OK or PLO_ERR_RANGE (*err_item = the lowest offending item).
-extern "C" int emu_nm_batch(const plo_batch_in *in, const plo_batch_out *lift, const uint64_t *item_seq_off, const uint8_t *rev_seq, const plo_index_desc *ix,
-                            unsigned order_seed, unsigned item_seed, uint32_t *item_nm, uint64_t *n_cmp, uint32_t *err_item) {
-    DevBatch bt;
-    DevWork wk;
-    fill_work(bt, wk, in, lift);
-    std::vector<int> clen(ix->n_chroms ? ix->n_chroms : 1, 0);
-    for (uint32_t c = 0; c < ix->n_chroms; ++c) clen[c] = (int)ix->chrom_len[c];
-    DevNm d;
-    memset(&d, 0, sizeof(d));
-    d.item_seq_off = item_seq_off;
-    d.rev_seq = rev_seq;
-    d.chrom_seq = ix->chrom_seq;
-    d.chrom_len = clen.data();
-    d.n_chroms = ix->n_chroms;
-    d.item_nm = item_nm;
-    return run_nm(bt, wk, d, order_seed, item_seed, n_cmp, err_item);
+// the source fields of DevNm, DevMd and DevEqx
+AlnSrc fill_src(const uint64_t *item_seq_off, const uint8_t *rev_seq, const uint8_t *const *chrom_seq, const int *chrom_len, uint32_t n_chroms) {
+    AlnSrc s;
+    memset(&s, 0, sizeof(s));
+    s.item_seq_off = item_seq_off;
+    s.rev_seq = rev_seq;
+    s.chrom_seq = chrom_seq;
+    s.chrom_len = chrom_len;
+    s.n_chroms = n_chroms;
+    return s;
 }
 
-// one item on its own: ops[n_ops], the record's bases seq[(l_seq + 1) / 2] (flip != 0: handed over as the reversed bases of the finishing,
-// otherwise as the batch's), the chromosome ref[chrom_len] and the item's position on it.  -> PLO_OK / PLO_ERR_RANGE
-extern "C" int emu_nm_one(const uint32_t *ops, uint32_t n_ops, const uint8_t *seq, uint32_t l_seq, int flip, const uint8_t *ref, int chrom_len, int64_t ref_pos,
-                          unsigned order_seed, uint32_t *nm, uint64_t *n_cmp) {
-    const uint32_t zero = 0;
-    const uint64_t off0 = 0, seq_off = flip ? 0 : PLO_NO_FLIP;
-    const uint8_t lifted = PLO_ITEM_LIFTED;
+// a whole batch and its source: `lift` = host arrays of a lift result, item_seq_off / rev_seq = emu_finish_batch's, `ix` = the index
+// description (its chromosomes)
+struct BatchWalk {
     DevBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    bt.read_seq_len = &l_seq;
-    bt.read_seq_off = &off0;
-    bt.seq = flip ? nullptr : seq;
-    bt.seq_bytes = flip ? 0 : (l_seq + 1) / 2;
-    bt.seg_read = &zero;
-    bt.seq_fmt = PLO_SEQ_BAM4;
-    bt.n_reads = bt.n_segs = 1;
     DevWork wk;
-    memset(&wk, 0, sizeof(wk));
-    wk.n_items = 1;
-    wk.item_seg = (uint32_t *)&zero;
-    wk.status = (uint8_t *)&lifted;
-    wk.chrom = (uint32_t *)&zero;
-    wk.pos = &ref_pos;
-    wk.cig_off = (uint64_t *)&off0;
-    wk.cig_len = &n_ops;
-    wk.out_cigar = (uint32_t *)ops;
+    std::vector<int> clen;
+    AlnSrc src;
+    BatchWalk(const plo_batch_in *in, const plo_batch_out *lift, const uint64_t *item_seq_off, const uint8_t *rev_seq, const plo_index_desc *ix)
+        : clen(ix->n_chroms ? ix->n_chroms : 1, 0) {
+        fill_work(bt, wk, in, lift);
+        for (uint32_t c = 0; c < ix->n_chroms; ++c) clen[c] = (int)ix->chrom_len[c];
+        src = fill_src(item_seq_off, rev_seq, ix->chrom_seq, clen.data(), ix->n_chroms);
+    }
+};
+
+// one item on its own: ops[n_ops], the record's bases seq[(l_seq + 1) / 2] (flip != 0: handed over as the reversed bases of the finishing,
+// otherwise as the batch's), the chromosome ref[chrom_len] and the item's position on it
+struct OneWalk {
+    const uint32_t zero = 0;
+    const uint64_t off0 = 0;
+    const uint8_t lifted = PLO_ITEM_LIFTED;
+    uint32_t n_ops, l_seq;
+    uint64_t seq_off;
+    const uint8_t *ref;
+    int chrom_len;
+    int64_t ref_pos;
+    DevBatch bt;
+    DevWork wk;
+    AlnSrc src;
+    OneWalk(const uint32_t *ops, uint32_t n_ops_, const uint8_t *seq, uint32_t l_seq_, int flip, const uint8_t *ref_, int chrom_len_, int64_t ref_pos_)
+        : n_ops(n_ops_), l_seq(l_seq_), seq_off(flip ? 0 : PLO_NO_FLIP), ref(ref_), chrom_len(chrom_len_), ref_pos(ref_pos_) {
+        memset(&bt, 0, sizeof(bt));
+        bt.read_seq_len = &l_seq;
+        bt.read_seq_off = &off0;
+        bt.seq = flip ? nullptr : seq;
+        bt.seq_bytes = flip ? 0 : (l_seq + 1) / 2;
+        bt.seg_read = &zero;
+        bt.seq_fmt = PLO_SEQ_BAM4;
+        bt.n_reads = bt.n_segs = 1;
+        memset(&wk, 0, sizeof(wk));
+        wk.n_items = 1;
+        wk.item_seg = (uint32_t *)&zero;
+        wk.status = (uint8_t *)&lifted;
+        wk.chrom = (uint32_t *)&zero;
+        wk.pos = &ref_pos;
+        wk.cig_off = (uint64_t *)&off0;
+        wk.cig_len = &n_ops;
+        wk.out_cigar = (uint32_t *)ops;
+        src = fill_src(&seq_off, flip ? seq : nullptr, &ref, &chrom_len, 1);
+    }
+    OneWalk(const OneWalk &) = delete;
+};
+}  // namespace
+
+// a whole batch (BatchWalk).  item_nm: [n_items].  Returns PLO_OK or PLO_ERR_RANGE (*err_item = the lowest offending item).
+extern "C" int emu_nm_batch(const plo_batch_in *in, const plo_batch_out *lift, const uint64_t *item_seq_off, const uint8_t *rev_seq, const plo_index_desc *ix,
+                            unsigned order_seed, unsigned item_seed, uint32_t *item_nm, uint64_t *n_cmp, uint32_t *err_item) {
+    const BatchWalk b(in, lift, item_seq_off, rev_seq, ix);
     DevNm d;
     memset(&d, 0, sizeof(d));
-    d.item_seq_off = &seq_off;
-    d.rev_seq = flip ? seq : nullptr;
-    d.chrom_seq = &ref;
-    d.chrom_len = &chrom_len;
-    d.n_chroms = 1;
+    static_cast<AlnSrc &>(d) = b.src;
+    d.item_nm = item_nm;
+    return run_nm(b.bt, b.wk, d, order_seed, item_seed, n_cmp, err_item);
+}
+
+// one item on its own (OneWalk).  -> PLO_OK / PLO_ERR_RANGE
+extern "C" int emu_nm_one(const uint32_t *ops, uint32_t n_ops, const uint8_t *seq, uint32_t l_seq, int flip, const uint8_t *ref, int chrom_len, int64_t ref_pos,
+                          unsigned order_seed, uint32_t *nm, uint64_t *n_cmp) {
+    const OneWalk w(ops, n_ops, seq, l_seq, flip, ref, chrom_len, ref_pos);
+    DevNm d;
+    memset(&d, 0, sizeof(d));
+    static_cast<AlnSrc &>(d) = w.src;
     d.item_nm = nm;
     uint32_t err_item;
-    return run_nm(bt, wk, d, order_seed, order_seed ? 1u : 0u, n_cmp, &err_item);
+    return run_nm(w.bt, w.wk, d, order_seed, order_seed ? 1u : 0u, n_cmp, &err_item);
 }
 
 // emu_records_build (tests/emu/emu_records.cpp) with DevRecords::item_nm: the records with NM:i behind ZM:C.  item_nm NULL: the same call.

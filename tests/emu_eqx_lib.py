@@ -21,7 +21,7 @@ _FLAGS = enl._FLAGS
 
 
 def _sources():
-    return [os.path.join(_HERE, "emu", "emu_eqx.cpp")] + eml._sources() + [os.path.join(ROOT, "portello_amd", "csrc", "eqx_core.hpp")]
+    return [os.path.join(_HERE, "emu", "emu_eqx.cpp")] + eml._sources() + [os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("eqx_core.hpp", "aln_walk.hpp")]
 
 
 def build(force=False):

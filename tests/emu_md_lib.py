@@ -20,7 +20,7 @@ _FLAGS = enl._FLAGS
 
 
 def _sources():
-    return [os.path.join(_HERE, "emu", "emu_md.cpp")] + enl._sources() + [os.path.join(ROOT, "portello_amd", "csrc", "md_core.hpp")]
+    return [os.path.join(_HERE, "emu", "emu_md.cpp")] + enl._sources() + [os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("md_core.hpp", "aln_walk.hpp")]
 
 
 def build(force=False):

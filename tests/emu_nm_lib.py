@@ -20,7 +20,7 @@ _FLAGS = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pr
 
 def _sources():
     return [os.path.join(_HERE, "emu", "emu_nm.cpp"), os.path.join(_HERE, "emu", "emu_records.cpp"), os.path.join(_HERE, "emu", "plo_wave.hpp")] + [
-        os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("nm_core.hpp", "records_core.hpp", "finish_core.hpp", "lift_core.hpp", "lift_types.hpp")] + [
+        os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("nm_core.hpp", "aln_walk.hpp", "records_core.hpp", "finish_core.hpp", "lift_core.hpp", "lift_types.hpp")] + [
         os.path.join(ROOT, "include", "portello_liftover.h")]
 
 

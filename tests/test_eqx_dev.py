@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import emu_eqx_lib as eel
+import emu_md_lib as eml
 import emu_nm_lib as enl
 import eqx_expect as ex
 import md_expect as mx
@@ -235,6 +236,27 @@ def test_hand_made_items(tmp_path):
     for (c, _), w, (st, got) in zip(cases, wants, res):
         assert st == abi.PLO_OK and np.array_equal(got, w), c.name
     assert [(st, len(got)) for st, got in res[len(cases):]] == [(abi.PLO_ERR_RANGE, 0)] * len(bad)
+
+
+def test_three_walks_agree():
+    """the invariant eqx_core.hpp states, on what the three emulated walks hand out (no model in between): the bases under X plus the I and D
+    lengths are NM, the X positions are the MD letters that do not stand behind '^', and the = / X CIGAR keeps the reference and read length"""
+    def lengths(ops):
+        t, l = ops & 15, (ops >> 4).astype(np.int64)
+        return int(l[np.isin(t, (0, 2, 3, 7, 8))].sum()), int(l[np.isin(t, (0, 1, 4, 7, 8))].sum())
+
+    for c, _ in all_cases():
+        for seed in (0, 5):
+            st_nm, nm, _ = enl.nm_one(c, seed)
+            st_md, _, md = eml.md_one(c, seed)
+            st_eqx, _, eqx = eel.eqx_one(c, seed)
+            assert (st_nm, st_md, st_eqx) == (abi.PLO_OK,) * 3, (c.name, seed)
+            assert ex.n_edits(eqx) == nm, (c.name, seed)
+            assert ex.x_positions(eqx) == ex.md_mismatch_positions(md), (c.name, seed)
+            assert lengths(eqx) == lengths(c.ops), (c.name, seed)
+    for c in tnd.refusal_cases():
+        for seed in (0, 5):
+            assert (enl.nm_one(c, seed)[0], eml.md_one(c, seed)[0], eel.eqx_one(c, seed)[0]) == (abi.PLO_ERR_RANGE,) * 3, (c.name, seed)
 
 
 # ---- 3. the 65 535 boundary through the record builder ---------------------------------------------------------------------------------

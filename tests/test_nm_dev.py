@@ -178,6 +178,12 @@ def hand_cases():
     iu_codes = np.repeat(np.arange(16, dtype=np.uint8), n)
     for p in (0, 3):
         out.append(enl.Case(f"iupac@{p}", M(f"{16 * n - p}M"), iu_codes[p:], iu_ref, p))
+    # the op search over several trips with many ops per trip: two steps of 64 ops, some three pieces for each of a step's 32 M ops
+    codes = np.concatenate([np.concatenate([near(ref[5 + 40 * i:45 + 40 * i], rng), rng.integers(0, 16, 1, dtype=np.uint8)]) for i in range(64)])
+    out.append(enl.Case("40M1I x 64", np.array(list(cg.encode("40M1I")) * 64, np.uint32), codes, ref, 5))
+    # the same with D ops between the matches (MD deals their pieces too)
+    codes = np.concatenate([near(ref[11 + 19 * i:28 + 19 * i], rng) for i in range(40)])
+    out.append(enl.Case("17M2D x 40", np.array(list(cg.encode("17M2D")) * 40, np.uint32), codes, ref, 11))
     return out
 
 
