@@ -506,7 +506,8 @@ def test_inflate_dev(sample):
     io, _ = d.inflate(data[:len(data) - 40], len(plain))
     assert int(io.bgzf_consumed) == ecl.bgzf_walk(data[:len(data) - 40], 1 << 40)[1] < len(data) - 40
     assert int(d.inflate(b"", 100)[0].n_blocks) == 0
-    # a damaged CRC, a damaged deflate stream and a damaged magic are PLO_ERR_IO; the text names the block's offset
+    # a damaged CRC and a damaged magic are PLO_ERR_IO; the text names the block's offset (a deflate stream that does not decode:
+    # test_inflate_crafted.py::test_dev_refused_stream, one per status of inflate.hpp)
     bad = bytearray(data)
     bad[blks[1][0] + (blks[1][1] - blks[1][0]) + blks[1][2]] ^= 0x55  # first CRC byte of block 1
     with pytest.raises(api.PortelloError) as e:
