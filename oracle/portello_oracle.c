@@ -1086,7 +1086,7 @@ int orc_finish_batch(const plo_batch_in *in, const plo_finish_in *fin, const plo
         flag[i] = f;
         nl[r] += 1;
         if (pitem[r] == UINT32_MAX || lift->item_mapq[pitem[r]] < lift->item_mapq[i]) pitem[r] = i; /* :338-345 first max wins */
-        if (lift->item_need_flipped[i]) {
+        if (lift->item_need_flipped[i] && in->read_seq_len[r]) {   /* a read without bases has nothing to reverse: no slot */
             uint32_t len = in->read_seq_len[r];
             isoff[i] = so;
             iqoff[i] = qo;
@@ -1106,10 +1106,12 @@ int orc_finish_batch(const plo_batch_in *in, const plo_finish_in *fin, const plo
             if (f & 0x10) {                                    /* :330-332 */
                 f ^= 0x10;
                 uint32_t len = in->read_seq_len[r];
-                rsoff[r] = so;
-                rqoff[r] = qo;
-                so += pad16(in->seq_fmt == PLO_SEQ_BAM4 ? (len + 1) / 2 : len);
-                qo += pad16(len);
+                if (len) {
+                    rsoff[r] = so;
+                    rqoff[r] = qo;
+                    so += pad16(in->seq_fmt == PLO_SEQ_BAM4 ? (len + 1) / 2 : len);
+                    qo += pad16(len);
+                }
             }
             uflag[r] = f;
         }
@@ -1176,9 +1178,9 @@ static void sb_putf(sbuf *b, const char *fmt, ...) {
 }
 /* :292-301 get_sa_tag_segment: "{chrom},{pos+1},{schar},{cigar},{mapq},0;" */
 static void sa_tag_segment(sbuf *b, const char *chrom, int64_t pos, int is_reverse, const uint32_t *cig, uint32_t n, unsigned mapq) {
-    static const char opc[] = "MIDNSHP=X";
+    static const char opc[] = "MIDNSHP=XB"; /* the ten ops the SAM specification names (the lift writes no B; the device code spells it so) */
     sb_putf(b, "%s,%lld,%c,", chrom, (long long)(pos + 1), is_reverse ? '-' : '+');
-    for (uint32_t k = 0; k < n; ++k) sb_putf(b, "%u%c", (unsigned)CIG_LEN(cig[k]), CIG_OP(cig[k]) < 9 ? opc[CIG_OP(cig[k])] : '?');
+    for (uint32_t k = 0; k < n; ++k) sb_putf(b, "%u%c", (unsigned)CIG_LEN(cig[k]), CIG_OP(cig[k]) < 10 ? opc[CIG_OP(cig[k])] : '?');
     sb_putf(b, ",%u,0;", mapq);
 }
 int orc_sa_values(const plo_batch_in *in, const plo_batch_out *lift, const uint16_t *item_flag, const char *const *chrom_names,

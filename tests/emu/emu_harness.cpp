@@ -435,95 +435,9 @@ extern "C" void emu_free_last() {
     g_last_emu_out = nullptr;
 }
 
-// ---- record finishing (finish_core.hpp) run on the host: what k_finish_items / k_finish_reads / k_finish_offsets /
-// k_revcomp do on the GPU, with plain loops standing in for the threads ------------------------------------------------
-namespace {
-struct FinOut {
-    std::vector<uint16_t> flag, bin, uflag;
-    std::vector<int64_t> rend;
-    std::vector<uint8_t> prim, rseq, rqual;
-    std::vector<uint64_t> isoff, iqoff, rsoff, rqoff;
-    std::vector<uint32_t> iread, nl, pitem, su, qu, soff, qoff, fflag, frank, flist;
-};
-FinOut *g_fin = nullptr;
-}  // namespace
-
-extern "C" int emu_finish_batch(const plo_batch_in *in, const plo_finish_in *fin, const plo_batch_out *lift, int nthreads,
-                                plo_finish_out *out) {
-    DevBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    bt.read_seq_len = in->read_seq_len;
-    bt.read_seq_off = in->read_seq_off;
-    bt.seq = in->seq;
-    bt.seq_fmt = in->seq_fmt;
-    bt.seq_bytes = in->seq_bytes;
-    bt.seg_read = in->seg_read;
-    bt.n_reads = in->n_reads;
-    bt.n_segs = in->n_segs;
-    DevWork wk;
-    memset(&wk, 0, sizeof(wk));
-    uint32_t n = lift->n_items, nr = in->n_reads, ne = n + nr;
-    wk.n_items = n;
-    wk.item_seg = (uint32_t *)lift->item_seg;
-    wk.status = (uint8_t *)lift->item_status;
-    wk.flip = (uint8_t *)lift->item_need_flipped;
-    wk.mapq = (uint8_t *)lift->item_mapq;
-    wk.pos = (int64_t *)lift->item_ref_pos;
-    wk.cig_off = (uint64_t *)lift->item_cigar_off;
-    wk.cig_len = (uint32_t *)lift->item_cigar_len;
-    wk.out_cigar = (uint32_t *)lift->cigar;
-    delete g_fin;
-    FinOut *o = g_fin = new FinOut();
-    size_t a = n ? n : 1, b = nr ? nr : 1, e = ne ? ne : 1;
-    o->flag.assign(a, 0); o->bin.assign(a, 0); o->rend.assign(a, 0); o->prim.assign(a, 0); o->isoff.assign(a, 0); o->iqoff.assign(a, 0);
-    o->iread.assign(a, 0); o->nl.assign(b, 0); o->pitem.assign(b, 0); o->uflag.assign(b, 0); o->rsoff.assign(b, 0); o->rqoff.assign(b, 0);
-    o->su.assign(e, 0); o->qu.assign(e, 0); o->soff.assign(e + 1, 0); o->qoff.assign(e + 1, 0); o->fflag.assign(e, 0);
-    o->frank.assign(e + 1, 0); o->flist.assign(e, 0);
-    DevFinish f;
-    memset(&f, 0, sizeof(f));
-    unsigned n_fault = 0;
-    f.n_fault = &n_fault;
-    f.read_flags = fin->read_flags; f.qual = fin->qual; f.read_qual_off = fin->read_qual_off; f.qual_bytes = fin->qual_bytes;
-    f.seq_bytes = in->seq_bytes;
-    f.item_flag = o->flag.data(); f.item_bin = o->bin.data(); f.item_ref_end = o->rend.data(); f.item_is_primary = o->prim.data();
-    f.item_seq_off = o->isoff.data(); f.item_qual_off = o->iqoff.data(); f.item_read = o->iread.data();
-    f.read_n_lifted = o->nl.data(); f.read_primary_item = o->pitem.data(); f.read_unmapped_flag = o->uflag.data();
-    f.read_seq_off = o->rsoff.data(); f.read_qual_off_out = o->rqoff.data();
-    f.su = o->su.data(); f.qu = o->qu.data(); f.soff = o->soff.data(); f.qoff = o->qoff.data();
-    f.fflag = o->fflag.data(); f.frank = o->frank.data(); f.flist = o->flist.data();
-    for (uint32_t i = 0; i < n; ++i) finish_item(bt, wk, f, i);
-    for (uint32_t r = 0; r < nr; ++r) finish_read(bt, wk, f, r);
-    for (uint32_t k = 0; k < ne; ++k) {
-        o->soff[k + 1] = o->soff[k] + o->su[k];
-        o->qoff[k + 1] = o->qoff[k] + o->qu[k];
-        o->frank[k + 1] = o->frank[k] + o->fflag[k];
-    }
-    for (uint32_t k = 0; k < ne; ++k) {
-        uint64_t so = o->su[k] ? (uint64_t)o->soff[k] * 16u : PLO_NO_FLIP, qo = o->qu[k] ? (uint64_t)o->qoff[k] * 16u : PLO_NO_FLIP;
-        if (o->su[k]) o->flist[o->frank[k]] = k;
-        if (k < n) { o->isoff[k] = so; o->iqoff[k] = qo; } else { o->rsoff[k - n] = so; o->rqoff[k - n] = qo; }
-    }
-    // 16-byte aligned destination buffers (vector of uint64 pairs)
-    o->rseq.assign((size_t)o->soff[ne] * 16 + 32, 0xEE);
-    o->rqual.assign((size_t)o->qoff[ne] * 16 + 32, 0xEE);
-    uint8_t *rs = o->rseq.data() + ((16 - ((uintptr_t)o->rseq.data() & 15)) & 15);
-    uint8_t *rq = o->rqual.data() + ((16 - ((uintptr_t)o->rqual.data() & 15)) & 15);
-    f.rev_seq = rs;
-    f.rev_qual = rq;
-    for (uint32_t k = 0; k < o->frank[ne]; ++k) {
-        uint32_t en = o->flist[k];
-        uint32_t read = en < n ? o->iread[en] : en - n;
-        for (int t = 0; t < nthreads; ++t)
-            revcomp_record(bt, f, read, rs + (uint64_t)o->soff[en] * 16u, rq + (uint64_t)o->qoff[en] * 16u, t, nthreads);
-    }
-    out->item_flag = f.item_flag; out->item_bin = f.item_bin; out->item_ref_end = f.item_ref_end; out->item_is_primary = f.item_is_primary;
-    out->item_seq_off = f.item_seq_off; out->item_qual_off = f.item_qual_off; out->read_n_lifted = f.read_n_lifted;
-    out->read_primary_item = f.read_primary_item; out->read_unmapped_flag = f.read_unmapped_flag; out->read_seq_off = f.read_seq_off;
-    out->read_qual_off = f.read_qual_off_out; out->rev_seq = rs; out->rev_qual = rq;
-    out->rev_seq_bytes = (uint64_t)o->soff[ne] * 16u; out->rev_qual_bytes = (uint64_t)o->qoff[ne] * 16u;
-    out->n_items = n; out->n_reads = ne - n;
-    return 0;
-}
+// record finishing and SA text (finish_core.hpp) run on the host: emu_finish_batch, emu_sa_segments, emu_sa_free (shared with the
+// sanitizer program emu_finish.cpp)
+#include "emu_finish.hpp"
 
 // the device comp_base (lift_core.hpp), for an exhaustive comparison with the oracle
 extern "C" int emu_comp_base(int b) { return plo::comp_base(b); }
@@ -582,48 +496,6 @@ extern "C" int emu_map_build(const uint32_t *cigar, uint32_t n, long long ref_po
         if (wv::lane() == 0) cnt = c;
     });
     return cnt;
-}
-
-
-// SA tag segments: finish_core.hpp's sa_item_len / sa_item_emit executed on the host.  `lift` and the finish arrays are host
-// copies; text/off are malloc'ed and released by emu_sa_free.
-extern "C" int emu_sa_segments(const plo_batch_out *lift, const uint16_t *item_flag, const uint32_t *item_read, const uint32_t *read_n_lifted,
-                               const uint32_t *chrom_name_off, const uint8_t *chrom_names, uint32_t **off_out, uint8_t **text_out) {
-    DevWork wk;
-    memset(&wk, 0, sizeof(wk));
-    wk.n_items = lift->n_items;
-    wk.status = (uint8_t *)lift->item_status;
-    wk.chrom = (uint32_t *)lift->item_chrom_index;
-    wk.pos = (int64_t *)lift->item_ref_pos;
-    wk.mapq = (uint8_t *)lift->item_mapq;
-    wk.cig_off = (uint64_t *)lift->item_cigar_off;
-    wk.cig_len = (uint32_t *)lift->item_cigar_len;
-    wk.out_cigar = (uint32_t *)lift->cigar;
-    uint32_t n = lift->n_items;
-    std::vector<uint32_t> len(n + 1, 0);
-    uint32_t *off = (uint32_t *)malloc(((size_t)n + 1) * 4);
-    DevSa sa;
-    sa.chrom_name_off = chrom_name_off;
-    sa.chrom_names = chrom_names;
-    sa.item_flag = item_flag;
-    sa.item_read = item_read;
-    sa.read_n_lifted = read_n_lifted;
-    sa.len = len.data();
-    sa.off = off;
-    sa.text = nullptr;
-    for (uint32_t i = 0; i < n; ++i) len[i] = sa_item_len(wk, sa, i);
-    off[0] = 0;
-    for (uint32_t i = 0; i < n; ++i) off[i + 1] = off[i] + len[i];
-    uint8_t *text = (uint8_t *)malloc(off[n] ? off[n] : 1);
-    sa.text = text;
-    for (uint32_t i = 0; i < n; ++i) sa_item_emit(wk, sa, i);
-    *off_out = off;
-    *text_out = text;
-    return 0;
-}
-extern "C" void emu_sa_free(uint32_t *off, uint8_t *text) {
-    free(off);
-    free(text);
 }
 
 // the block-map searches of the descriptor code (enumerate.hpp) on one sorted key array: kv_upper_bound, kv_lower_bound,

@@ -15,7 +15,8 @@ _lib = None
 
 
 def build(force=False, sanitize=False):
-    srcs = [os.path.join(_HERE, "emu", "emu_harness.cpp"), os.path.join(_HERE, "emu", "plo_wave.hpp"), os.path.join(_HERE, "emu", "emu_inflate.hpp")] + [
+    srcs = [os.path.join(_HERE, "emu", "emu_harness.cpp"), os.path.join(_HERE, "emu", "plo_wave.hpp"), os.path.join(_HERE, "emu", "emu_inflate.hpp"),
+            os.path.join(_HERE, "emu", "emu_finish.hpp")] + [
         os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("lift_core.hpp", "lane_core.hpp", "lane_stream.hpp", "inflate.hpp", "finish_core.hpp", "lift_types.hpp", "index_pack.hpp", "enumerate.hpp")]
     stale = (not os.path.exists(_LIB)) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs)
     if force or stale:
@@ -56,7 +57,8 @@ def liftover_batch(index: abi.IndexData, batch: abi.BatchData, stages=abi.STAGES
 
 
 def finish_batch(batch: abi.BatchData, read_flags, qual, read_qual_off, lift: abi.BatchResult, nthreads=7) -> dict:
-    """finish_core.hpp executed on the host (plain loops instead of GPU threads)"""
+    """finish_core.hpp executed on the host (plain loops instead of GPU threads).  "n_fault": the items that ended LEN_MISMATCH, PANIC
+    or NEED_BASES (plo_finish_batch_dev refuses such a batch; the emulation finishes it all the same)"""
     b = batch.to_desc()
     rf = np.ascontiguousarray(read_flags, dtype=np.uint16)
     q = np.ascontiguousarray(qual, dtype=np.uint8)
@@ -73,13 +75,15 @@ def finish_batch(batch: abi.BatchData, read_flags, qual, read_qual_off, lift: ab
         setattr(lo, n, p(arrs[n], t))
     lo.n_cigar = len(arrs["cigar"])
     out = abi.PloFinishOut()
-    assert lib().emu_finish_batch(C.byref(b), C.byref(fin), C.byref(lo), nthreads, C.byref(out)) == 0
+    n_fault = lib().emu_finish_batch(C.byref(b), C.byref(fin), C.byref(lo), nthreads, C.byref(out))
+    assert n_fault >= 0
     n, nr = lift.n_items, batch.n_reads
     cp = lambda ptr, dt, cnt: np.ctypeslib.as_array(ptr, shape=(cnt,)).astype(dt, copy=True) if cnt else np.zeros(0, dt)
     res = {name: cp(getattr(out, name), dt, n) for name, dt in abi.FINISH_ITEM_FIELDS}
     res.update({name: cp(getattr(out, name), dt, nr) for name, dt in abi.FINISH_READ_FIELDS})
     res["rev_seq"] = cp(out.rev_seq, np.uint8, int(out.rev_seq_bytes))
     res["rev_qual"] = cp(out.rev_qual, np.uint8, int(out.rev_qual_bytes))
+    res["n_fault"] = n_fault
     return res
 
 
