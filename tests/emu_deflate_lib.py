@@ -31,7 +31,7 @@ def build(force=False):
 
 
 def build_asan(force=False):
-    """the same code as a program with AddressSanitizer and UBSan (CPU only): emu_deflate_asan IN OUT LEVEL"""
+    """the same code as a program with AddressSanitizer and UBSan (CPU only): emu_deflate_asan IN OUT LEVEL | --jobs JOBS OUT LEVEL"""
     srcs = _sources()
     if force or _stale(_ASAN, srcs):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
@@ -48,6 +48,12 @@ def lib():
         L.emu_bgzf_deflate.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_uint, C.POINTER(C.c_uint32)]
         L.emu_bgzf_slot.restype = C.c_uint32
         L.emu_bgzf_work_bytes.restype = C.c_uint32
+        L.emu_def_build_code.restype = C.c_int
+        L.emu_def_build_code.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]
+        L.emu_def_put.restype = C.c_int
+        L.emu_def_put.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint, C.c_void_p]
+        L.emu_def_symbols.restype = None
+        L.emu_def_symbols.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -91,3 +97,84 @@ def run_asan(data: bytes, level: int, tmp_dir: str):
     if pr.returncode != 0:
         return pr.returncode, pr.stderr, b""
     return 0, pr.stderr, open(pout, "rb").read()
+
+
+# ---- direct entries ------------------------------------------------------------------------------------------------------------------------
+PUT_GUARD = 4  # words behind cap_words that emu_def_put must leave alone
+
+
+def build_code(freq, limit: int, order_seed: int = 0):
+    """def_build_code over `freq` as a wave -> (lengths, codes as they enter the stream: bit-reversed)"""
+    import numpy as np
+
+    n = len(freq)
+    f = np.ascontiguousarray(freq, np.uint32)
+    ln, code = np.full(n, 0xEE, np.uint8), np.full(n, 0xEEEE, np.uint16)
+    rc = lib().emu_def_build_code(f.ctypes.data, n, limit, order_seed, ln.ctypes.data, code.ctypes.data)
+    assert rc == 0, rc
+    return [int(x) for x in ln], [int(x) for x in code]
+
+
+def put(calls, cap_words: int, order_seed: int = 0):
+    """calls: a list of wave-wide def_put calls, each a list of 64 (value, bits) -> (the cap_words words as bytes, bits written, open word);
+    the words behind cap_words are checked"""
+    import numpy as np
+
+    v = np.array([[c[0] for c in call] for call in calls], np.uint64).reshape(-1)
+    nb = np.array([[c[1] for c in call] for call in calls], np.uint32).reshape(-1)
+    assert len(v) == 64 * len(calls)
+    out = np.full(cap_words + PUT_GUARD, 0x5A5A5A5A, np.uint32)
+    out[:cap_words] = 0
+    res = np.zeros(2, np.uint32)
+    rc = lib().emu_def_put(v.ctypes.data, nb.ctypes.data, len(calls), out.ctypes.data, cap_words, order_seed, res.ctypes.data)
+    assert rc == 0, rc
+    assert np.all(out[cap_words:] == 0x5A5A5A5A), "def_put wrote behind cap_words"
+    return out[:cap_words].tobytes(), int(res[0]), int(res[1])
+
+
+def symbols():
+    """(lens[256][3], dists[32768][3], extra[59]): def_len_code / def_dist_code over their domains, def_len_extra / def_dist_extra"""
+    import numpy as np
+
+    lens, dists, extra = np.zeros((256, 3), np.uint32), np.zeros((32768, 3), np.uint32), np.zeros(59, np.uint32)
+    lib().emu_def_symbols(lens.ctypes.data, dists.ctypes.data, extra.ctypes.data)
+    return lens, dists, extra
+
+
+def job_payload(p: bytes) -> bytes:
+    import struct
+
+    return struct.pack("<II", 1, len(p)) + p
+
+
+def job_table(freq, limit: int) -> bytes:
+    import struct
+
+    return struct.pack(f"<III{len(freq)}I", 2, len(freq), limit, *freq)
+
+
+def job_put(calls, cap_words: int) -> bytes:
+    import struct
+
+    flat = [c for call in calls for c in call]
+    return struct.pack("<III", 3, len(calls), cap_words) + struct.pack(f"<{len(flat)}Q", *[c[0] for c in flat]) + struct.pack(f"<{len(flat)}I", *[c[1] for c in flat])
+
+
+def run_asan_jobs(jobs: bytes, level: int, tmp_dir: str):
+    """(return code, stderr, list of the records' results) of the sanitizer build over a file of job records (emu_deflate.cpp, run_jobs)"""
+    import struct
+
+    exe = build_asan()
+    pin, pout = os.path.join(tmp_dir, "def_asan_jobs.bin"), os.path.join(tmp_dir, "def_asan_jobs_out.bin")
+    with open(pin, "wb") as fh:
+        fh.write(jobs)
+    pr = subprocess.run([exe, "--jobs", pin, pout, str(level)], capture_output=True, text=True, timeout=900)
+    if pr.returncode != 0:
+        return pr.returncode, pr.stderr, []
+    raw, at, out = open(pout, "rb").read(), 0, []
+    while at < len(raw):
+        n = struct.unpack_from("<I", raw, at)[0]
+        out.append(raw[at + 4:at + 4 + n])
+        at += 4 + n
+    assert at == len(raw)
+    return 0, pr.stderr, out
