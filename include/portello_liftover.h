@@ -263,9 +263,14 @@ plo_status plo_ctx_set_phase_events(plo_ctx *ctx, int on);
 plo_status plo_liftover_batch(plo_ctx *ctx, const plo_batch_in *in, uint32_t stages, plo_batch_out *out);
 /* Device buffers in, device (context-owned) buffers out; returns after the result sizes are known, output is
    complete on the context's stream (call plo_ctx_sync or synchronise the stream before reading it).
-   The batch is checked on the device before any lift kernel runs: an index outside its array -> PLO_ERR_INVALID_ARG;
-   a coordinate outside the 31-bit BAM range, an op code above 8, a CIGAR spanning more than 2^30 bases or more than
-   2^31 - 1 ops / item weights in the batch -> PLO_ERR_RANGE. */
+   The batch is checked on the device before any lift kernel runs.
+   PLO_ERR_INVALID_ARG: an index outside its array -- a seg_cigar_off entry below its predecessor or above
+   seg_cigar_off[n_segs] among them.
+   PLO_ERR_RANGE: a coordinate outside the 31-bit BAM range (seg_pos below 0 or above 0x7ffffff0); an op code above 8; a CIGAR
+   spanning 2^30 bases or more (the last span accepted is 2^30 - 1); a read segment that ends behind its contig's end and
+   meets a reverse-strand contig segment (rev_pos, src/read_alignment_scanner.rs:164-166, would be negative: the reference
+   panics there); more than 2^31 - 1 ops / item weights in the batch.
+   A batch with faults of both kinds, in whichever segments, gets PLO_ERR_INVALID_ARG. */
 plo_status plo_liftover_batch_dev(plo_ctx *ctx, const plo_batch_in *in, uint32_t stages, plo_batch_out *out);
 
 /* ------------------------------------------------------------------------------------------------------------

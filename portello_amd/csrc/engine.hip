@@ -76,8 +76,9 @@ using namespace plo;
 #endif
 constexpr uint32_t SEG_LANES = PLO_SEG_LANES, SEG_UNROLL = 32 / SEG_LANES < 2 ? 2 : 32 / SEG_LANES;
 // It is also the boundary check of the device path (the kernels index with what the batch says): bit 0 of *err = an index
-// outside its array (PLO_ERR_INVALID_ARG), bit 1 = a coordinate outside the 31-bit BAM range, an op code above 8 or a CIGAR
-// spanning more than 2^30 bases (PLO_ERR_RANGE) -- what the reference's types rule out by construction.
+// outside its array (PLO_ERR_INVALID_ARG), bit 1 = a coordinate outside the 31-bit BAM range, an op code above 8, a CIGAR
+// spanning 2^30 bases or more, or (raised by the descriptor kernels) a negative rev_pos (PLO_ERR_RANGE) -- what the
+// reference's types rule out by construction.
 enum { VERR_INDEX = 1u, VERR_RANGE = 2u, VERR_CAP = 4u };
 __global__ __launch_bounds__(256) void k_seg_count(DevIndex ix, DevBatch bt, uint32_t *seg_cnt, int *seg_reflen, uint32_t *seg_readlen,
                                                    uint32_t *seg_nm, uint32_t *err) {
@@ -119,6 +120,10 @@ __global__ __launch_bounds__(256) void k_seg_count(DevIndex ix, DevBatch bt, uin
     uint32_t pairs = 0, carry = 0;
     constexpr uint32_t OPL = 32 / SEG_LANES;  // (a multiple of 4: 16-byte loads)
     const uint32_t n_ops_all = bt.n_segs ? bt.seg_cigar_off[bt.n_segs] : 0u;
+    if (c1 > n_ops_all) {  // (offsets that are not monotone further on: the segment's ops would end behind the batch's -- none are read)
+        bad |= VERR_INDEX;
+        c1 = c0;
+    }
     for (uint32_t base = c0; base < c1; base += SEG_LANES * OPL) {
         const uint32_t my = base + OPL * sub;
         uint32_t c[OPL];
@@ -207,7 +212,9 @@ __global__ void k_item_emit(DevIndex ix, DevBatch bt, DevWork wk, uint32_t stage
     seg_info_level0(si, bt, wk, stages, s);
     if (o0 == o1) return;  // (no items -- among them the segments whose contig the index does not know: nothing below is indexed by it)
     seg_info_level1(si, ix, bt, wk, stages, s);
-    emit_segment_items(ix, wk, stages, s, o0, (long long)ref_len, si);
+    bool neg = false;
+    emit_segment_items(ix, wk, stages, s, o0, (long long)ref_len, si, &neg);
+    if (neg) atomicOr(err, (uint32_t)VERR_RANGE);  // (a read segment behind its contig's end on a reverse-strand contig segment: enumerate.hpp)
 }
 
 // Block maps of the contig segments, built on the device at index creation: ONE WAVE per contig split segment walks its contig->reference
@@ -242,7 +249,7 @@ __global__ void k_item_desc(DevIndex ix, DevBatch bt, DevWork wk, uint32_t stage
             return;
         }
     }
-    build_item_desc(ix, bt, wk, stages, i, seg, in_cseg[i], segment_ref_len(bt, seg));
+    if (!build_item_desc(ix, bt, wk, stages, i, seg, in_cseg[i], segment_ref_len(bt, seg))) atomicOr(err, (uint32_t)VERR_RANGE);
 }
 
 // ---- device-wide exclusive scan of uint32 (three launches; out has n+1 entries, out[n] = total) -------------------
@@ -2795,7 +2802,7 @@ plo_status plo_liftover_batch_dev(plo_ctx *c, const plo_batch_in *in, uint32_t s
             c->err = "plo_batch_in: an index points outside its array (seg_read / seg_contig / seg_cigar_off / read_seq_off / item_seg / item_cseg)";
             return PLO_ERR_INVALID_ARG;
         }
-        c->err = "plo_batch_in: coordinate outside the 31-bit BAM range, CIGAR op code above 8, or a CIGAR spanning more than 2^30 bases";
+        c->err = "plo_batch_in: coordinate outside the 31-bit BAM range, CIGAR op code above 8, a CIGAR spanning 2^30 bases or more, or a read segment that ends behind its contig's end on a reverse-strand contig segment";
         return PLO_ERR_RANGE;
     };
     {   // k_seg_count always runs: it is the boundary check of the batch (and counts the items unless the caller lists them)
@@ -3542,7 +3549,7 @@ static plo_status liftover_fast(plo_ctx *c, const plo_batch_in *in, uint32_t sta
             c->err = "plo_batch_in: an index points outside its array (seg_read / seg_contig / seg_cigar_off / read_seq_off / item_seg / item_cseg)";
             return PLO_ERR_INVALID_ARG;
         }
-        c->err = "plo_batch_in: coordinate outside the 31-bit BAM range, CIGAR op code above 8, or a CIGAR spanning more than 2^30 bases";
+        c->err = "plo_batch_in: coordinate outside the 31-bit BAM range, CIGAR op code above 8, a CIGAR spanning 2^30 bases or more, or a read segment that ends behind its contig's end on a reverse-strand contig segment";
         return PLO_ERR_RANGE;
     }
     const unsigned long long all_ops = (unsigned long long)hx[6] | ((unsigned long long)hx[7] << 32);

@@ -352,7 +352,10 @@ PLO_DEV CsegInfo cseg_info(const DevIndex &ix, uint32_t gseg) {
 // Resolves everything the tile kernel needs to know about item i = (read segment seg, contig segment cseg):
 // the caller glue of get_liftover_alignment_for_read_and_contig_segment (src/read_alignment_scanner.rs:146-176) --
 // need_flipped (:153-157), rev_pos (:164-166) -- plus the window of the block map the item can touch.
-PLO_DEV void build_item_desc(const DevIndex &ix, const DevWork &wk, uint32_t stages, uint32_t i, uint32_t seg, uint32_t cseg, long long ref_len,
+// Returns false for an item whose rev_pos is negative: a read segment that ends behind its contig's end, met by a reverse-strand contig
+// segment.  The reference casts that position to usize and panics in the block map's range query; the batch is refused (the item is still
+// described: on the one-round-trip path the lift kernels run before the host sees the flag).
+PLO_DEV bool build_item_desc(const DevIndex &ix, const DevWork &wk, uint32_t stages, uint32_t i, uint32_t seg, uint32_t cseg, long long ref_len,
                              const SegInfo &s, const CsegInfo &c) {
     const bool contig_fwd = c.is_fwd != 0;
     bool flip = false, rev = false;
@@ -409,27 +412,29 @@ PLO_DEV void build_item_desc(const DevIndex &ix, const DevWork &wk, uint32_t sta
     wk.flip[i] = (uint8_t)flip;
     wk.mapq[i] = c.mapq;
     wk.chrom[i] = c.chrom;
+    return pos1 >= 0;
 }
 // (an item of an explicit list: the three levels one after the other)
-PLO_DEV void build_item_desc(const DevIndex &ix, const DevBatch &bt, const DevWork &wk, uint32_t stages, uint32_t i, uint32_t seg,
+PLO_DEV bool build_item_desc(const DevIndex &ix, const DevBatch &bt, const DevWork &wk, uint32_t stages, uint32_t i, uint32_t seg,
                              uint32_t cseg, long long ref_len) {
     SegInfo s;
     seg_info_level0(s, bt, wk, stages, seg);
     seg_info_level1(s, ix, bt, wk, stages, seg);
-    build_item_desc(ix, wk, stages, i, seg, cseg, ref_len, s, cseg_info(ix, s.g0 + cseg));
+    return build_item_desc(ix, wk, stages, i, seg, cseg, ref_len, s, cseg_info(ix, s.g0 + cseg));
 }
 
 // The items of one read segment, in contig-segment order, resolved at out_off (`s`: both levels loaded; the batch has been validated
-// and the segment has items).  Returns their number.
+// and the segment has items).  Returns their number; *neg (when given) is set if one of them has a negative rev_pos (build_item_desc).
 PLO_DEV uint32_t emit_segment_items(const DevIndex &ix, const DevWork &wk, uint32_t stages, uint32_t seg, uint32_t out_off, long long ref_len,
-                                    const SegInfo &s) {
+                                    const SegInfo &s, bool *neg = nullptr) {
     const long long r_start = s.pos, r_end = r_start + ref_len;
     uint32_t n = 0;
     for (uint32_t g = s.g0; g < s.g1; ++g) {
         const CsegInfo c = cseg_info(ix, g);
         // segment_range.intersect_range(&read_range): other.end >= self.start && other.start < self.end
         if ((r_end >= (long long)c.start) & (r_start < (long long)c.end)) {
-            build_item_desc(ix, wk, stages, out_off + n, seg, g - s.g0, ref_len, s, c);
+            const bool ok = build_item_desc(ix, wk, stages, out_off + n, seg, g - s.g0, ref_len, s, c);
+            if (neg && !ok) *neg = true;
             ++n;
         }
     }
@@ -438,8 +443,9 @@ PLO_DEV uint32_t emit_segment_items(const DevIndex &ix, const DevWork &wk, uint3
 
 // Counts (and, when wk != nullptr, resolves at out_off) the items of one read segment, in contig-segment order.
 // `ref_len_cache`: per-segment reference spans; written by the counting pass (wk == nullptr), read by the emit pass.
+// `neg`: as emit_segment_items'.
 PLO_DEV uint32_t enumerate_segment(const DevIndex &ix, const DevBatch &bt, uint32_t seg, const DevWork *wk, uint32_t stages,
-                                   uint32_t out_off, int *ref_len_cache = nullptr, bool have_ref_len = false) {
+                                   uint32_t out_off, int *ref_len_cache = nullptr, bool have_ref_len = false, bool *neg = nullptr) {
     uint32_t contig = bt.seg_contig[seg];
     if (contig >= ix.n_contigs) return 0;
     uint32_t g0 = ix.contig_seg_off[contig], g1 = ix.contig_seg_off[contig + 1];
@@ -455,7 +461,7 @@ PLO_DEV uint32_t enumerate_segment(const DevIndex &ix, const DevBatch &bt, uint3
         SegInfo s;
         seg_info_level0(s, bt, *wk, stages, seg);
         seg_info_level1(s, ix, bt, *wk, stages, seg);
-        return emit_segment_items(ix, *wk, stages, seg, out_off, ref_len, s);
+        return emit_segment_items(ix, *wk, stages, seg, out_off, ref_len, s, neg);
     }
     long long r_start = (long long)bt.seg_pos[seg];
     long long r_end = r_start + ref_len;

@@ -28,6 +28,9 @@ struct Out {
 extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in *in, uint32_t stages, int cap, int window,
                                   int big_thresh, int big_cap, unsigned order_seed, int mid_waves, int mid_cap, int lane_max_w, int lane_capw,
                                   int lane_heavy_per, int lane_budget, int lane_stream, plo_batch_out *out, unsigned long long *counters_out) {
+    // Returns 0, 1 (the index does not pack), 2 (a kernel raised CNT_ERROR) or 3 (an item has a negative rev_pos: the card answers
+    // PLO_ERR_RANGE; the result handed out is what its lift kernels compute before the host sees the flag).  The other batch checks of
+    // k_seg_count have no counterpart here: the caller sends accepted batches.
     // lane_stream (with lane_heavy_per > 0, all stages): the heavy classes through the streaming kernel (lane_stream.hpp) -- teams of three waves, 1: the GPU's
     // rings, 2: the smallest Q2 the code allows (unreleased tails outgrow it: retry list)
     // lane_max_w >= 0: items up to that weight run through the lane-per-item code (lane_core.hpp) with an LDS slice of lane_capw
@@ -153,13 +156,16 @@ extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in 
     wk.huge_list = huge_list.data();
     wk.miss_list = miss_list.data();
     const bool sp = in->seq_fmt == PLO_SEQ_BAM4_SPARSE;  // (sparse bases: such items keep PLO_ITEM_NEED_BASES here, the second look is the engine's)
+    // an item with a negative rev_pos (build_item_desc): k_item_emit / k_item_desc raise PLO_ERR_RANGE for the batch.  The batch is lifted
+    // here all the same -- on the one-round-trip path the card's lift kernels run before the host sees the flag -- and the refusal is returned
+    bool neg_rev_pos = false;
     if (in->item_seg) {
         for (uint32_t i = 0; i < n_items; ++i)
-            build_item_desc(ix, bt, wk, stages, i, in->item_seg[i], in->item_cseg[i], segment_ref_len(bt, in->item_seg[i]));
+            if (!build_item_desc(ix, bt, wk, stages, i, in->item_seg[i], in->item_cseg[i], segment_ref_len(bt, in->item_seg[i]))) neg_rev_pos = true;
     } else {
         uint32_t off = 0;
         for (uint32_t s = 0; s < in->n_segs; ++s) {
-            if (seg_cnt[s]) enumerate_segment(ix, bt, s, &wk, stages, off);
+            if (seg_cnt[s]) enumerate_segment(ix, bt, s, &wk, stages, off, nullptr, false, &neg_rev_pos);
             off += seg_cnt[s];
         }
     }
@@ -425,7 +431,7 @@ extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in 
     // the Out object stays alive until emu_free_last()
     extern void *g_last_emu_out;
     g_last_emu_out = o;
-    return counters[CNT_ERROR] ? 2 : 0;
+    return counters[CNT_ERROR] ? 2 : neg_rev_pos ? 3 : 0;  // (3: lifted in full, but the card refuses the batch with PLO_ERR_RANGE)
 }
 
 void *g_last_emu_out = nullptr;
