@@ -10,7 +10,9 @@
 //   k_chunk_sort         light items by weight inside windows of 128 positions of the class order (groups of similar length)
 //   k_lift_lanes         DOMINANT KERNEL on HiFi batches (lane_core.hpp): persistent waves, 64 light items per wave (32 / 16 / 8 when the
 //                        batch has few), one LANE per item, the whole shift / liftover / length check / simplify pipeline in place in a
-//                        ~180-byte LDS region per item
+//                        ~180-byte LDS region per item; the shift stage of items whose ops alternate match / lone indel (nearly all of
+//                        HiFi data) runs as a lockstep loop over the clusters, lengths changed in place (PLO_LANE_LOCKSTEP=0: every
+//                        item through the event-aligned walk)
 //   k_lift_lanes_g       heavy items of batches with many of them (dominant on the stress workload): the same lane-per-item code, the
 //                        regions in wave-private global scratch behind per-lane LDS windows (lane_core.hpp, LaneWin)
 //   (heavy items of smaller batches)   scan of the weights, k_max_u32 (weight histogram -> tile geometry, host sync), k_tile_bounds,
@@ -1852,6 +1854,7 @@ struct plo_ctx {
     int lane_static_rounds = 0;  // 0: by the launch's rounds (lane_ticket_arm); > 0: that many; < 0: fixed slots only
     int lane_tail_rounds = 1;  // PLO_LANE_TAIL: rounds' worth of cheap groups (no shift stage) dealt last (0: classes one to one)
     int lane_kvs = LANE_KVS;  // block-map entries staged per wave (PLO_LANE_KVS: 64 .. LANE_KVS_MAX)
+    bool lane_lockstep = true;  // PLO_LANE_LOCKSTEP=0: the shift stage walks every item event by event (lane_core.hpp; A/B runs of the lockstep loop)
     bool lane_h16 = false;    // PLO_LANE_H16=1: 16-bit regions (k_lift_lanes16; stage sets with the liftover)
     bool lane_stats = false;  // PLO_LANE_STATS=1: the light-item kernel that counts algorithmic bytes and lane utilisation (k_lift_lanes_stats)
     int lane_sort_window = LANE_SORT_WINDOW;
@@ -2505,6 +2508,7 @@ plo_status plo_ctx_create(const plo_index *ix, void *hip_stream, plo_ctx **out) 
     if (const char *e = getenv("PLO_LANE_TAIL")) c->lane_tail_rounds = std::max(0, atoi(e));
     if (const char *e = getenv("PLO_LANE_KVS")) c->lane_kvs = std::min(LANE_KVS_MAX, std::max(64, atoi(e) & ~63));
     if (!c->lane_h16) c->lane_kvs = std::min(c->lane_kvs, LANE_KVS);
+    if (const char *e = getenv("PLO_LANE_LOCKSTEP")) c->lane_lockstep = atoi(e) != 0;
     if (const char *e = getenv("PLO_LANE_SORT_WINDOW")) c->lane_sort_window = c->lane_budget_window = std::min(2048, std::max(64, atoi(e) & ~63));
     if (const char *e = getenv("PLO_LANE_BUDGET")) c->lane_budget = atoi(e) != 0;
     if (const char *e = getenv("PLO_LANE_HEAVY_MIN")) c->lane_heavy_min = atoi(e);
@@ -2670,6 +2674,7 @@ static lane_kernel_t lane_kernel_of(const plo_ctx *c, uint32_t stages, bool sp) 
 // descriptor, CIGAR and block-map lines in its L2, which the tickets give up; the last rounds are what levels the waves.
 static void lane_ticket_arm(plo_ctx *c, DevWork &wk, uint32_t groups, uint32_t waves) {
     wk.lane_kvs = (uint32_t)c->lane_kvs;
+    wk.lane_lockstep_off = c->lane_lockstep ? 0u : 1u;
     wk.lane_tail_rounds = (uint32_t)c->lane_tail_rounds;
     wk.lane_ticket = nullptr;
     wk.lane_ticket_next = nullptr;

@@ -38,6 +38,12 @@
 #define PLO_MARK(s) asm volatile("; " s)  // a comment in the ISA listing (tools: hipcc -S), no code
 #endif
 
+// PLO_SHIFT_LOCKSTEP: the shift stage's lockstep loop for items whose ops alternate match / lone indel (lane_tile, "LEFT SHIFT,
+// clean items"); 0 compiles it out, DevWork::lane_lockstep_off switches it off at run time.
+#ifndef PLO_SHIFT_LOCKSTEP
+#define PLO_SHIFT_LOCKSTEP 1
+#endif
+
 namespace plo {
 
 // (plo_safe_words, enumerate.hpp: where the lanes without a usable probe window point their unconditional loads)
@@ -878,6 +884,136 @@ PLO_DEV void lane_tile(const DevIndex &ix, const DevBatch &bt, const DevWork &wk
         // The emission of a cluster (M I D, :132-147) needs its homology; the probe is sent when the cluster ends and the cluster
         // stays `pend`ing -- match bases that follow collect in `msince` -- until the lane's next event: its probe's HBM round trip
         // runs under the scan in between.
+        // CLEAN items (on HiFi data all but a few in a thousand), in LOCKSTEP: iteration j is every lane's j-th cluster, at the
+        // known index 2j + 1 behind the lane's first match.  M(a0) X1 M(a1) .. Xn M(an) becomes M(a0 - s1) X1 M(s1 + a1 - s2) .. Xn M(sn + an)
+        // with s_j = min(s_{j-1} + a_{j-1}, h_j): the builder's arithmetic (`match` = shift carried + bases since, :132, :150-153) without
+        // its scan, its cluster state and its writer -- the ops stay where they are, only the matches' lengths change.  The probe's
+        // addresses come from the input walk alone, so the window of cluster j + 1 is asked for before cluster j is resolved (two probes,
+        // alternating: nothing in flight changes registers at the back edge); only the clamp needs the carry.
+        // A lane whose shift EMPTIES a match (the builder skips that op; its neighbours meet, the leading edge rule may apply) finishes the
+        // arithmetic all the same and then streams its region through the writer, which is the builder's push sequence exactly.
+        constexpr bool LOCK = PLO_SHIFT_LOCKSTEP && !WIN && !H16 && !SP && !NOSHIFT;
+        if constexpr (LOCK) {
+            // Which lanes are clean: (S|H)* M (X M)* (S|H)* over the stored ops, X one I or one D, every length > 0, no two equal
+            // neighbours (the writer would merge them), hence no N and no P.  Three short loops over the region: the leading clips, the
+            // (M, X) pairs -- two ops per trip --, the trailing clips.
+            const bool lk = shift_on & (wk.lane_lockstep_off == 0u);
+            int n_lead = 0, lead_read = 0, ncl = 0;  // leading clip ops, the read bases they consume; clusters
+            bool c_bad = false;
+            const int end = cur_off + n;
+            if (wv::ballot(lk) != 0ull) {
+                {
+                    bool go = lk;
+                    int pt = -1;
+                    while (wv::ballot(go) != 0ull) {
+                        const bool have = go & (n_lead < n);
+                        const uint32_t c = R[have ? cur_off + n_lead : 0];
+                        const int t = op_type(c);
+                        const bool clip = have & ((unsigned)(t - (int)OP_S) < 2u);
+                        c_bad = c_bad | (clip & ((c < 16u) | (t == pt)));
+                        lead_read += clip ? op_len(c) : 0;
+                        n_lead += clip ? 1 : 0;
+                        pt = t;
+                        go = clip;
+                    }
+                }
+                {
+                    bool go = lk;
+                    while (wv::ballot(go) != 0ull) {
+                        const int i0 = cur_off + n_lead + 2 * ncl;
+                        const bool h0 = go & (i0 < end), h1 = go & (i0 + 1 < end);
+                        const uint32_t c0 = R[h0 ? i0 : 0], c1 = R[h1 ? i0 + 1 : 0];
+                        const bool m = h0 & b_is_match(op_type(c0)) & (c0 >= 16u);
+                        const bool x = h1 & b_is_indel(op_type(c1)) & (c1 >= 16u);
+                        c_bad = c_bad | (go & !m);  // (behind an X, or first of all, a match must stand)
+                        go = m & x;                 // (else: the end, a clip, or something the loop below refuses)
+                        ncl += go ? 1 : 0;
+                    }
+                }
+                {
+                    int k = cur_off + n_lead + 2 * ncl + 1, pt = -1;
+                    const bool go = lk & !c_bad;
+                    while (wv::ballot(go & (k < end)) != 0ull) {
+                        const bool have = go & (k < end);
+                        const uint32_t c = R[have ? k : 0];
+                        const int t = op_type(c);
+                        c_bad = c_bad | (have & (((unsigned)(t - (int)OP_S) >= 2u) | (c < 16u) | (t == pt)));
+                        pt = have ? t : pt;
+                        k += have ? 1 : 0;
+                    }
+                }
+            }
+            const bool lock_on = lk & !c_bad;
+            if (wv::ballot(lock_on) != 0ull) {
+                const uint8_t *const sref = (const uint8_t *)(uintptr_t)shift_ref;
+                const int m0 = lock_on ? cur_off + n_lead : 0;  // the lane's first match
+                int ref_head = pos1, read_head = lead_read, carry = 0, probes = 0;
+                bool marked = false;
+                LaneProbe pa, pb;
+                int a_a = 0, a_b = 0;  // the ORIGINAL length of the match in front of the probe's cluster
+                // cluster j: heads, panic test and the window's loads
+                auto issue = [&](LaneProbe &p, int &a, int j) {
+                    const bool on = lock_on & (j < ncl);
+                    const uint32_t cm = R[on ? m0 + 2 * j : 0], cx = R[on ? m0 + 2 * j + 1 : 0];
+                    const int t = op_type(cx), L = op_len(cx);
+                    a = op_len(cm);
+                    const int rs = ref_head + a, qs = read_head + a;
+                    const int del = t == OP_D ? L : 0, ins = t == OP_I ? L : 0;
+                    // (no clamp yet: maxk = min(rs, qs), 0 where the reference panics; the clamp s + a > 0 does not change which lanes load)
+                    lane_probe_arm(p, on, shift_ref_len, rs, del, rd, qs, ins, IMAX, panic);
+                    lane_probe_load(p, on, sref, shift_ref_len, rd, (const uint8_t *)plo_safe_words);
+                    ref_head = on ? rs + del : ref_head;
+                    read_head = on ? qs + ins : read_head;
+                };
+                auto resolve = [&](LaneProbe &p, int a, int j) {
+                    const bool on = lock_on & (j < ncl);
+                    const int bound = carry + a;
+                    p.maxk = wv::imin(p.maxk, bound);
+                    int h = lane_probe_finish(p, on, sref, shift_ref_len, rd, probes);
+                    h = rd.miss ? 0 : h;
+                    const int sh = wv::imin(bound, h);  // actual_shift_len (:132)
+                    if (on) R[m0 + 2 * j] = mk_op(OP_M, bound - sh);
+                    marked = marked | (on & (bound == sh));
+                    carry = on ? sh : carry;
+                };
+                PLO_MARK("LOCKSTEP LOOP BEGIN");
+                issue(pa, a_a, 0);
+                for (int j = 0; wv::ballot(lock_on & (j < ncl)) != 0ull; j += 2) {
+                    PLO_LC(8, 2)
+                    if constexpr (STATS) {
+                        ctx.u_act += (unsigned)__builtin_popcountll(wv::ballot(lock_on & (j < ncl))) + (unsigned)__builtin_popcountll(wv::ballot(lock_on & (j + 1 < ncl)));
+                        ctx.u_trips += 2;
+                    }
+                    issue(pb, a_b, j + 1);
+                    resolve(pa, a_a, j);
+                    issue(pa, a_a, j + 2);
+                    resolve(pb, a_b, j + 1);
+                }
+                PLO_MARK("LOCKSTEP LOOP END");
+                if (lock_on) R[m0 + 2 * ncl] = mk_op(OP_M, op_len(R[m0 + 2 * ncl]) + carry);  // the last match takes the last shift (every match is written, as M: a lone = or X of the input too)
+                if constexpr (STATS) algo += lock_on ? 2u * (unsigned)probes : 0u;
+                const bool mk = lock_on & marked;
+                if (wv::ballot(mk) != 0ull) {  // read at cur_off, written at gap: behind the reader
+                    LaneOut o;
+                    wr_open(o, gap);
+                    const int wl0 = cur_off - gap;
+                    const int nmax = wv::reduce_max(mk ? n : 0);
+                    for (int k = 0; k < nmax; ++k) {
+                        const bool act = mk & (k < n);
+                        const uint32_t c = R[cur_off + (act ? k : 0)];
+                        lane_push<false, ST, H16>(o, act & (op_len(c) > 0), op_type(c), op_len(c), wl0 + k + 1);
+                    }
+                    wr_finish(o, mk, gap, wl0 + n);
+                    if (mk) {
+                        n = o.no;
+                        cur_off = gap;
+                        pos += o.lead_shift;
+                        ovf = ovf | o.ovf;
+                    }
+                }
+                shift_on = shift_on & !lock_on;  // clean lanes keep cur_off, n and pos; the others take the walk below
+            }
+        }
         if constexpr (!NOSHIFT) if (wv::ballot(shift_on) != 0ull) {
             const uint8_t *const sref = (const uint8_t *)(uintptr_t)shift_ref;
             LaneOut o;

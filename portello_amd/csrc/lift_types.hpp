@@ -127,6 +127,7 @@ struct DevWork {
     uint32_t lane_static_rounds;
     uint32_t lane_tail_rounds;  // rounds' worth of groups without the shift stage kept for the end of the launch (0: the classes one to one, the longer one's rest last)
     uint32_t lane_kvs;  // block-map entries a wave of the light-item kernel stages in LDS (0: LANE_KVS; a multiple of 64 up to LANE_KVS_MAX)
+    uint32_t lane_lockstep_off;  // != 0: the shift stage's lockstep loop for clean items is not taken (lane_core.hpp; 0, the default of a zeroed struct: taken)
 };
 
 }  // namespace plo
