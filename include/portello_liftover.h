@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLO_API_VERSION 19 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file; 18: plo_runs_merge_plan_dev / plo_runs_merge_emit_dev (sorted windows merged into large runs on the device); 19: plo_depth_* (the depth of the records: difference array, scan, windows, runs) */
+#define PLO_API_VERSION 20 /* 4: plo_timing starts with struct_size (the callee fills no more than the caller's struct holds); 5: plo_gather_*, plo_ctx_set_stats (plo_timing::algo_bytes / lane_utilisation of light items only on request), plo_ctx_stream / plo_ctx_device; 6: plo_ctx_set_phase_events; 7: plo_records_build_dev, plo_bam_window_batch_raw; 8: plo_bgzf_compress_dev, plo_bam_write_blocks; 9: plo_batch_build_dev, plo_bam_window_raw; 10: plo_bgzf_inflate_dev, plo_window_cut_dev; 11: plo_bgzf_inflate_part_dev, plo_window_cut_part_dev, plo_part_start_dev; 12: plo_nm_dev (NM:i on the records of plo_records_build_dev); 13: plo_md_dev (MD:Z on them, the source's MD cut); 14: plo_records_sort_dev (the window's records in coordinate order), plo_bam_output_header_so, plo_bam_merge_runs; 15: plo_records_index_dev (what a BAM index needs of every record of a sorted buffer), plo_bam_writer_index_enable / _index_add, plo_bam_merge_runs_indexed; 16: plo_eqx_dev (= / X CIGARs on the records of plo_records_build_dev); 17: plo_fasta_* (the reference FASTA loaded on the device), plo_fasta_load_file; 18: plo_runs_merge_plan_dev / plo_runs_merge_emit_dev (sorted windows merged into large runs on the device); 19: plo_depth_* (the depth of the records: difference array, scan, windows, runs) */
 
 typedef enum plo_status {
     PLO_OK = 0,
@@ -706,6 +706,118 @@ plo_status plo_depth_finish_dev(plo_ctx *ctx, plo_depth *depth, float *finish_ms
 plo_status plo_depth_windows_dev(plo_ctx *ctx, plo_depth *depth, uint32_t window, plo_depth_windows_out *out);
 plo_status plo_depth_runs_dev(plo_ctx *ctx, plo_depth *depth, plo_depth_runs_out *out);
 plo_status plo_depth_reset(plo_ctx *ctx, plo_depth *depth);
+
+/* ---- Allele pileup and candidate sites (device-resident, opt-in; API version 20) -------------------------------------------
+ * Which reference bases carry non-reference evidence, taken from the records while they lie on the device (the inputs of plo_depth_add_dev)
+ * against the calling context's reference -- the front of a small-variant caller, and the check that a lift put its reads in the right
+ * place.  Only EVENTS are counted; the reference-matching count at a base is depth - (A + C + G + T + N).
+ * THE OBJECT.  A pileup object holds ONE int32 array with PLO_PILEUP_CHANNELS = 8 counters per reference base; a base's 32 bytes are
+ *   contiguous and 32-byte aligned:
+ *     0 A, 1 C, 2 G, 3 T   a mismatching read base A, C, G, T          5 DEL   deletions that begin at this base
+ *     4 N                  a mismatching read base of any other code   6 INS   insertions anchored at this base
+ *                                                                      7 CLIP  soft clips anchored at this base
+ *   It is created over a list of chromosomes (n_ref, ref_len[], the output header's @SQ order), like plo_depth_create, optionally with at
+ *   most ONE region [beg, end) per chromosome.  No regions: every chromosome is covered whole.  With regions a chromosome without one has
+ *   no bases in the object.  Chromosome r's slot holds slot_end[r] - slot_beg[r] bases and begins at base slot_off[r] of the array
+ *   (slot_off counts in BASES; the counter of channel ch of base b is array[(slot_off[r] + b - slot_beg[r]) * 8 + ch]).  An event outside
+ *   its chromosome's region is dropped silently: no error.  MEMORY: 32 bytes a base -- about 2 GB for chr20, about 99 GB for a whole genome
+ *   of 3.1 Gb; the regions exist for this reason.
+ *   plo_pileup_create -> PLO_ERR_INVALID_ARG for a negative ref_len, a region with ref_id outside [0, n_ref), with beg < 0, beg > end or
+ *   end > ref_len[ref_id], and for two regions on one chromosome.  n_ref == 0 is allowed.  opts NULL: the defaults.
+ * COUNTED RECORDS.  A record is counted iff refID >= 0, pos >= 0 and (FLAG & exclude_flags) == 0; exclude_flags defaults to 0x704, as for
+ *   depth.  Its ops are the record's REAL CIGAR as defined for depth.  A counted record whose real CIGAR consumes no reference adds nothing.
+ * WALKING THE OPS from pos, rf the reference position reached, rd the read position; ops of length 0 are ignored:
+ *   M, =, X   every one of the L base pairs is classified by plo_nm_dev's pair rule: c1 the read's 4-bit code, c2 the reference byte's code
+ *             in "=ACMGRSVTWYHKDBN" (any other byte: 15); the pair MATCHES iff c1 == 0, or c1 == c2 and c1 != 15.  The op's own code is
+ *             not trusted: X over matching bases adds nothing, = over a mismatch adds.  A mismatching pair at reference base b adds 1 to
+ *             [b][ch], ch = A, C, G, T for c1 = 1, 2, 4, 8 and N for every other c1.
+ *   D         adds 1 to [rf][DEL]: only the first deleted base.
+ *   I         adds 1 to [max(rf - 1, pos)][INS]: the VCF anchor -- the base in front, or the record's first base when none is in front.
+ *   S         adds 1 to [max(rf - 1, pos)][CLIP]: a leading clip lands on the first aligned base, a trailing one on the last.
+ *   N, H, P and the codes 9-15 add nothing.
+ * CHECKED for every record of an add, on the device, before anything is added; a record reports the first kind it breaks:
+ *   1 .. 8   exactly the kinds of plo_depth_add_dev, in its order
+ *   9        the bases and qualities leave the record: 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq > 4 + block_size
+ *   10       a counted record whose real CIGAR's read length (M I S = X) differs from l_seq
+ * Any -> PLO_ERR_INVALID_ARG, err_record the LOWEST such record, err_kind what it broke, and A REFUSED CALL ADDS NOTHING.
+ * CONTEXT.  The reference is the CALLING context's index: refID r is chromosome r of its chrom_seq (what plo_records_build_dev writes).
+ *   PLO_ERR_INVALID_ARG for an index without chrom_seq, an index whose chromosome count or lengths differ from the object's, and a context
+ *   of another device; more than 2^27 - 1 records in a call -> PLO_ERR_RANGE.
+ * plo_pileup_add_dev runs on the calling context's stream: a check and the add, a wave per record each.  The add takes the ops 64 a step,
+ *   cuts the M / = / X ops at the 16-byte lines of the reference and issues ONE int32 atomic add of device scope per event.  n_events is the
+ *   number of adds issued inside the regions.
+ * plo_pileup_sites_dev lists the candidate sites.  With m the maximum of count[ch] over the channels in channel_mask, base b is a site iff
+ *   m >= min_count, and depth == NULL or frac_num == 0 or m * frac_den >= frac_num * depth[b] (64-bit products; a depth of 0 passes).
+ *   `depth` is a FINISHED depth object over the same n_ref / ref_len, or NULL (then every site's depth is -1).  opts NULL: the defaults
+ *   (channel_mask 0x6F: A C G T DEL INS; min_count 1; frac_num 0).  PLO_ERR_INVALID_ARG for frac_den == 0 while frac_num != 0,
+ *   min_count < 1, an open depth object, a depth object with another chromosome list.  The sites are ordered by (ref_id, pos) and stay on
+ *   the DEVICE, owned by the object until its next sites call or reset (48 bytes a site); ref_base is the chrom_seq byte.
+ * NO STATES: there is no finish step; the sum of n_events since the last reset equals the sum of the array.  Adds commute, and adds from
+ *   several contexts of one device may overlap in time.  Sites, reset and destroy MUST NOT OVERLAP AN ADD: the caller's duty. */
+#define PLO_PILEUP_CHANNELS 8
+#define PLO_PILEUP_MASK_DEFAULT 0x6Fu
+
+typedef struct plo_pileup plo_pileup;
+
+typedef struct plo_pileup_region {
+    int32_t ref_id;
+    int32_t beg, end;             /* 0-based half-open */
+} plo_pileup_region;
+
+typedef struct plo_pileup_opts {
+    uint32_t exclude_flags;       /* a record with any of these FLAG bits is not counted */
+    uint32_t n_regions;           /* 0: every chromosome whole */
+    const plo_pileup_region *regions;
+} plo_pileup_opts;
+
+typedef struct plo_pileup_info {
+    int32_t *array;               /* device [n_bases * 8] */
+    uint64_t n_bases;             /* slot_off[n_ref] */
+    const uint64_t *slot_off;     /* HOST [n_ref + 1], in bases, owned by the object */
+    const int32_t *slot_beg;      /* HOST [n_ref] */
+    const int32_t *slot_end;      /* HOST [n_ref] */
+    uint64_t bytes_allocated;     /* device bytes the object holds now: the array, its tables, the sites and their scan */
+    uint32_t n_ref;
+    uint32_t exclude_flags;
+} plo_pileup_info;
+
+typedef struct plo_pileup_add_out {
+    uint32_t n_records;
+    uint32_t n_counted;           /* records the rule counts */
+    uint32_t err_record;          /* PLO_ERR_INVALID_ARG from the device check: lowest offending record, else UINT32_MAX */
+    uint32_t err_kind;            /* what it broke (1 .. 10 above), else 0 */
+    uint64_t n_events;            /* adds issued inside the regions */
+    float add_ms;                 /* HIP-event time of the call's two kernels */
+} plo_pileup_add_out;
+
+typedef struct plo_pileup_sites_opts {
+    uint32_t channel_mask;        /* bit ch: channel ch takes part in the maximum */
+    int32_t min_count;            /* >= 1 */
+    uint32_t frac_num, frac_den;  /* frac_num == 0: no fraction test */
+} plo_pileup_sites_opts;
+
+typedef struct plo_pileup_site {
+    int32_t ref_id;
+    int32_t pos;                  /* 0-based */
+    int32_t depth;                /* -1 without a depth object */
+    uint8_t ref_base;
+    uint8_t pad[3];
+    int32_t count[PLO_PILEUP_CHANNELS];
+} plo_pileup_site;
+
+typedef struct plo_pileup_sites_out {
+    const plo_pileup_site *site;  /* device [n_sites], ordered by (ref_id, pos) */
+    uint64_t n_sites;
+    float sites_ms;
+} plo_pileup_sites_out;
+
+plo_status plo_pileup_create(plo_ctx *ctx, uint32_t n_ref, const int32_t *ref_len, const plo_pileup_opts *opts, plo_pileup **out);
+void plo_pileup_destroy(plo_pileup *pileup);
+plo_status plo_pileup_info_get(const plo_pileup *pileup, plo_pileup_info *info);
+plo_status plo_pileup_reset(plo_ctx *ctx, plo_pileup *pileup);
+/* in: plo_depth_in's shape and meaning */
+plo_status plo_pileup_add_dev(plo_ctx *ctx, plo_pileup *pileup, const plo_depth_in *in, plo_pileup_add_out *out);
+plo_status plo_pileup_sites_dev(plo_ctx *ctx, plo_pileup *pileup, const plo_depth *depth, const plo_pileup_sites_opts *opts, plo_pileup_sites_out *out);
 
 /* ---- Sorted windows merged into large runs (device-resident, opt-in; API version 18) --------------------------------------
  * A k-way merge of coordinate-sorted record buffers -- typically copies of plo_sort_out::bytes / record_off of several windows -- that each

@@ -136,7 +136,7 @@ class PloBatchOut(C.Structure):
     ]
 
 
-PLO_API_VERSION = 19  # include/portello_liftover.h
+PLO_API_VERSION = 20  # include/portello_liftover.h
 
 
 class PloTiming(C.Structure):
@@ -300,6 +300,45 @@ DEPTH_RUN_DTYPE = np.dtype([("ref_id", "<i4"), ("beg", "<i4"), ("end", "<i4"), (
 
 class PloDepthRunsOut(C.Structure):
     _fields_ = [("run", C.POINTER(PloDepthRun)), ("n_runs", C.c_uint64), ("runs_ms", C.c_float)]
+
+
+PILEUP_CHANNELS = 8  # PLO_PILEUP_CHANNELS
+PILEUP_CHANNEL_NAMES = ("A", "C", "G", "T", "N", "DEL", "INS", "CLIP")
+PILEUP_MASK_DEFAULT = 0x6F  # PLO_PILEUP_MASK_DEFAULT: A C G T DEL INS
+
+
+class PloPileupRegion(C.Structure):
+    _fields_ = [("ref_id", C.c_int32), ("beg", C.c_int32), ("end", C.c_int32)]
+
+
+class PloPileupOpts(C.Structure):
+    _fields_ = [("exclude_flags", C.c_uint32), ("n_regions", C.c_uint32), ("regions", C.POINTER(PloPileupRegion))]
+
+
+class PloPileupInfo(C.Structure):
+    """array: device [n_bases * 8]; slot_off [n_ref + 1] (in bases), slot_beg and slot_end [n_ref]: HOST"""
+    _fields_ = [("array", C.POINTER(C.c_int32)), ("n_bases", C.c_uint64), ("slot_off", _u64p), ("slot_beg", C.POINTER(C.c_int32)), ("slot_end", C.POINTER(C.c_int32)),
+                ("bytes_allocated", C.c_uint64), ("n_ref", C.c_uint32), ("exclude_flags", C.c_uint32)]
+
+
+class PloPileupAddOut(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("n_counted", C.c_uint32), ("err_record", C.c_uint32), ("err_kind", C.c_uint32), ("n_events", C.c_uint64), ("add_ms", C.c_float)]
+
+
+class PloPileupSitesOpts(C.Structure):
+    _fields_ = [("channel_mask", C.c_uint32), ("min_count", C.c_int32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
+
+
+class PloPileupSite(C.Structure):
+    """48 bytes: ref_id, pos, depth (-1 without a depth object), ref_base, the eight counters"""
+    _fields_ = [("ref_id", C.c_int32), ("pos", C.c_int32), ("depth", C.c_int32), ("ref_base", C.c_uint8), ("pad", C.c_uint8 * 3), ("count", C.c_int32 * 8)]
+
+
+PILEUP_SITE_DTYPE = np.dtype([("ref_id", "<i4"), ("pos", "<i4"), ("depth", "<i4"), ("ref_base", "u1"), ("pad", "u1", (3,)), ("count", "<i4", (8,))])  # plo_pileup_site
+
+
+class PloPileupSitesOut(C.Structure):
+    _fields_ = [("site", C.POINTER(PloPileupSite)), ("n_sites", C.c_uint64), ("sites_ms", C.c_float)]
 
 
 class PloEqxOut(C.Structure):

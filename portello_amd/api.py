@@ -104,6 +104,18 @@ def load_library(path: Optional[str] = None):
     L.plo_depth_runs_dev.argtypes = [vp, vp, C.POINTER(abi.PloDepthRunsOut)]
     L.plo_depth_reset.restype = C.c_int
     L.plo_depth_reset.argtypes = [vp, vp]
+    L.plo_pileup_create.restype = C.c_int
+    L.plo_pileup_create.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(abi.PloPileupOpts), C.POINTER(vp)]
+    L.plo_pileup_destroy.restype = None
+    L.plo_pileup_destroy.argtypes = [vp]
+    L.plo_pileup_info_get.restype = C.c_int
+    L.plo_pileup_info_get.argtypes = [vp, C.POINTER(abi.PloPileupInfo)]
+    L.plo_pileup_reset.restype = C.c_int
+    L.plo_pileup_reset.argtypes = [vp, vp]
+    L.plo_pileup_add_dev.restype = C.c_int
+    L.plo_pileup_add_dev.argtypes = [vp, vp, C.POINTER(abi.PloDepthIn), C.POINTER(abi.PloPileupAddOut)]
+    L.plo_pileup_sites_dev.restype = C.c_int
+    L.plo_pileup_sites_dev.argtypes = [vp, vp, vp, C.POINTER(abi.PloPileupSitesOpts), C.POINTER(abi.PloPileupSitesOut)]
     L.plo_eqx_dev.restype = C.c_int
     L.plo_eqx_dev.argtypes = [vp, C.POINTER(abi.PloBatchIn), C.POINTER(abi.PloEqxOut)]
     L.plo_records_build_dev.restype = C.c_int

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libportello_liftover.so")
 SOURCES = ["engine.hip", "bam_host.cpp", "phase1.cpp", "gather_rccl.cpp"]
 LIBS = ["-lz", "-ldl"]
-HEADERS = ["plo_wave.hpp", "lift_core.hpp", "lane_core.hpp", "lane_stream.hpp", "inflate.hpp", "deflate.hpp", "finish_core.hpp", "records_core.hpp", "batch_core.hpp", "aln_walk.hpp", "nm_core.hpp", "md_core.hpp", "eqx_core.hpp", "sort_core.hpp", "merge_core.hpp", "index_core.hpp", "depth_core.hpp", "fasta_core.hpp", "window_core.hpp", "bgzf_walk.hpp", "lift_types.hpp", "index_pack.hpp", "enumerate.hpp", "bam_internal.hpp"]
+HEADERS = ["plo_wave.hpp", "lift_core.hpp", "lane_core.hpp", "lane_stream.hpp", "inflate.hpp", "deflate.hpp", "finish_core.hpp", "records_core.hpp", "batch_core.hpp", "aln_walk.hpp", "nm_core.hpp", "md_core.hpp", "eqx_core.hpp", "sort_core.hpp", "merge_core.hpp", "index_core.hpp", "depth_core.hpp", "pileup_core.hpp", "fasta_core.hpp", "window_core.hpp", "bgzf_walk.hpp", "lift_types.hpp", "index_pack.hpp", "enumerate.hpp", "bam_internal.hpp"]
 
 
 def hipcc() -> str:

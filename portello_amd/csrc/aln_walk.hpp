@@ -70,11 +70,11 @@ struct AlnStep {
     unsigned long long rd_end, rf_end;  // (uniform) consumed behind the step
 };
 
-PLO_DEV AlnStep aln_step(const AlnItem &it, uint32_t k, unsigned long long rd_done, unsigned long long rf_done) {
+// the step of the lane's op word c (has: the lane has one): the scans, the bounds check, the op's first read base and reference byte
+PLO_DEV AlnStep aln_step_op(const AlnItem &it, bool has, uint32_t c, unsigned long long rd_done, unsigned long long rf_done) {
     AlnStep s;
-    const int lane = wv::lane();
-    s.has = k + (uint32_t)lane < it.n;
-    s.c = s.has ? it.cg[k + lane] : 0u;
+    s.has = has;
+    s.c = s.has ? c : 0u;
     s.t = s.c & 15u;
     s.len = s.c >> 4;
     s.is_cmp = s.has && (s.t == 0 || s.t == 7 || s.t == 8);
@@ -87,6 +87,33 @@ PLO_DEV AlnStep aln_step(const AlnItem &it, uint32_t k, unsigned long long rd_do
     s.rd = rd_done + rd_inc - rd_adv;
     s.fa = it.ref0 + (uintptr_t)(rf_done + rf_inc - rf_adv);
     return s;
+}
+
+PLO_DEV AlnStep aln_step(const AlnItem &it, uint32_t k, unsigned long long rd_done, unsigned long long rf_done) {
+    const bool has = k + (uint32_t)wv::lane() < it.n;
+    return aln_step_op(it, has, has ? it.cg[k + wv::lane()] : 0u, rd_done, rf_done);
+}
+
+// A RECORD's view (pileup_core.hpp): l_seq bases at seq, ref0 the address of the reference byte at its position, ref_room the chromosome's
+// bytes from there on, n ops at cig.  A record lies at any byte address, so its ops are no aligned words: `cg` keeps the address only, and
+// the walk of such a view takes its steps with aln_step_bytes, never with aln_step.
+PLO_DEV AlnItem aln_open_record(const uint8_t *seq, unsigned long long lseq, uintptr_t ref0, unsigned long long ref_room, const uint8_t *cig, uint32_t n) {
+    AlnItem it;
+    it.ok = true;
+    it.seq = seq;
+    it.seq_lo = (uintptr_t)seq;
+    it.seq_hi = it.seq_lo + (uintptr_t)((lseq + 1) / 2);
+    it.lseq = lseq;
+    it.ref_room = ref_room;
+    it.ref0 = ref0;
+    it.cg = (const uint32_t *)(const void *)cig;
+    it.n = n;
+    return it;
+}
+// aln_step for a view opened by aln_open_record: the op is read a byte at a time
+PLO_DEV AlnStep aln_step_bytes(const AlnItem &it, uint32_t k, unsigned long long rd_done, unsigned long long rf_done) {
+    const bool has = k + (uint32_t)wv::lane() < it.n;
+    return aln_step_op(it, has, has ? rec_rd32((const uint8_t *)(const void *)it.cg + 4ull * (k + (uint32_t)wv::lane())) : 0u, rd_done, rf_done);
 }
 
 // the 16-byte lines that reference bytes [fa, fa + len) lie on, len > 0

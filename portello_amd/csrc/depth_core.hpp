@@ -119,13 +119,26 @@ struct DevDepth {
 };
 
 // ---- check ---------------------------------------------------------------------------------------------------------------------------------
-// Record i by one wave (i wave-uniform) -> 1 when it is counted and accepted.  Nothing outside [bytes, bytes + n_bytes) is read: the fixed
-// fields only behind sort_check_record, the in-record ops only behind index_cigar_fits, an aux byte only inside the record
-// (aux_field_len_wave), the ops of CG only behind that field's own length check.
-PLO_DEV unsigned depth_check_record(const DevDepth &d, uint32_t i) {
+// what the check learns of record i (all of it wave-uniform); pileup_core.hpp goes on from here
+struct DepthRec {
+    int kind;                 // 0, or the first of the kinds 1 .. 8 the record breaks
+    const uint8_t *p;         // the record (its block_size word)
+    unsigned long long len;   // its bytes
+    unsigned at, nc;          // the in-record CIGAR: its offset and its ops
+    const uint8_t *cig;       // the real CIGAR, n_cig ops (0 unless the record is counted)
+    uint32_t n_cig;
+    int ref, pos;
+    bool counted;
+    unsigned long long rlen;  // the reference length of the n_cig ops
+};
+// Record i by one wave (i wave-uniform).  Nothing outside [bytes, bytes + n_bytes) is read: the fixed fields only behind sort_check_record,
+// the in-record ops only behind index_cigar_fits, an aux byte only inside the record (aux_field_len_wave), the ops of CG only behind that
+// field's own length check.
+PLO_DEV DepthRec depth_check_rules(const DevSort &s, const int32_t *ref_len, uint32_t exclude_flags, uint32_t i) {
+    DepthRec r;
     unsigned long long key, len;
-    int kind = sort_check_record(d.s, i, key, len);
-    const uint8_t *p = d.s.bytes + (kind == SORT_ERR_OFFSET ? 0ull : d.s.record_off[i]);
+    int kind = sort_check_record(s, i, key, len);
+    const uint8_t *p = s.bytes + (kind == SORT_ERR_OFFSET ? 0ull : s.record_off[i]);
     unsigned at = 0, nc = 0;
     if (!kind && !index_cigar_fits(p, len, at, nc)) kind = DEPTH_ERR_CIGAR;
     const uint8_t *cig = p + at;
@@ -157,7 +170,7 @@ PLO_DEV unsigned depth_check_record(const DevDepth &d, uint32_t i) {
     if (!kind) {
         ref = (int)rec_rd32(p + 4);
         pos = (int)rec_rd32(p + 8);
-        counted = ref >= 0 && pos >= 0 && (rec_rd16(p + 18) & d.exclude_flags) == 0;
+        counted = ref >= 0 && pos >= 0 && (rec_rd16(p + 18) & exclude_flags) == 0;
     }
     if (!counted) n_cig = 0;  // (wave-uniform: the reductions below are reached by every lane either way)
     unsigned long long part = 0;
@@ -165,12 +178,28 @@ PLO_DEV unsigned depth_check_record(const DevDepth &d, uint32_t i) {
     for (unsigned long long k = (unsigned long long)wv::lane(); k < n_cig; k += PLO_WAVE) part += index_op_reflen(rec_rd32(cig + 4ull * k));
     // (below 2^58: fewer than 2^30 ops, the array of CG lies inside a record of less than 2^32 bytes, of less than 2^28 bases each)
     const unsigned long long rlen = wv::shfl(wave_scan_incl_u64(part), 63);
-    if (counted && (unsigned long long)pos + rlen > (unsigned long long)(uint32_t)d.ref_len[ref]) kind = DEPTH_ERR_END;
+    if (counted && (unsigned long long)pos + rlen > (unsigned long long)(uint32_t)ref_len[ref]) kind = DEPTH_ERR_END;
+    r.kind = kind;
+    r.p = p;
+    r.len = len;
+    r.at = at;
+    r.nc = nc;
+    r.cig = cig;
+    r.n_cig = n_cig;
+    r.ref = ref;
+    r.pos = pos;
+    r.counted = counted;
+    r.rlen = rlen;
+    return r;
+}
+// -> 1 when record i is counted and accepted; the lowest offender, or the record's plan word
+PLO_DEV unsigned depth_check_record(const DevDepth &d, uint32_t i) {
+    const DepthRec r = depth_check_rules(d.s, d.ref_len, d.exclude_flags, i);
     if (wv::lane() == 0) {
-        if (kind) wv::atomic_min(d.err, (int)((i << 4) | (unsigned)kind));
-        else d.plan[i] = ((unsigned long long)(cig - p) << 32) | n_cig;
+        if (r.kind) wv::atomic_min(d.err, (int)((i << 4) | (unsigned)r.kind));
+        else d.plan[i] = ((unsigned long long)(r.cig - r.p) << 32) | r.n_cig;
     }
-    return !kind && counted ? 1u : 0u;
+    return !r.kind && r.counted ? 1u : 0u;
 }
 
 // the records w, w + nw, ... by wave w of nw

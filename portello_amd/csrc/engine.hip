@@ -51,6 +51,7 @@
 #include "merge_core.hpp"
 #include "index_core.hpp"
 #include "depth_core.hpp"
+#include "pileup_core.hpp"
 #define PLO_FA_HOST 1
 #include "fasta_core.hpp"
 #include "window_core.hpp"
@@ -1422,6 +1423,17 @@ __global__ __launch_bounds__(256) void k_depth_runs(DevDepthRuns d, unsigned lon
     if (t < n_tiles) depth_runs_tile<EMIT>(d, t);
 }
 
+// ---- allele pileup (pileup_core.hpp): no LDS anywhere, no kernel waits on another workgroup -------------------------------------------------
+// a wave per record for the check and the add; the add's cost is its scattered atomics, one per event
+__global__ __launch_bounds__(256) void k_pileup_check(DevPileup d) { pileup_check_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+__global__ __launch_bounds__(256) void k_pileup_add(DevPileup d) { pileup_add_records(d, blockIdx.x * 4u + (uint32_t)wv::wave_id(), gridDim.x * 4u); }
+// a wave per tile of PLO_PILEUP_TILE bases.  HBM-bound by design: the array is read once by the count and once by the emit
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_pileup_sites(DevPileupSites d, unsigned long long n_tiles) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * 4u + (unsigned long long)wv::wave_id();
+    if (t < n_tiles) pileup_sites_tile<EMIT>(d, t);  // (wave-uniform)
+}
+
 // ---- the reference FASTA (fasta_core.hpp): a wave per tile of FA_TILE bytes, the tiles grid-strided over the waves; no LDS.  HBM-bound by
 // design: the piece is read by k_fa_lines, k_fa_count and k_fa_emit (k_fa_headers leaves the tiles without a header line alone), the bases
 // are written once
@@ -1751,6 +1763,22 @@ struct plo_depth {
     }
 };
 
+// plo_pileup_*: the allele counters of a list of chromosomes or of a region of each (pileup_core.hpp).  An object of its own, like plo_depth
+struct plo_pileup {
+    int device = 0;
+    uint32_t n_ref = 0;
+    uint32_t exclude_flags = PLO_DEPTH_EXCLUDE_DEFAULT;
+    std::vector<int32_t> ref_len, slot_beg, slot_end;
+    std::vector<uint64_t> slot_off;  // [n_ref + 1], in bases
+    unsigned long long n_bases = 0;
+    DevBuf arr, d_ref_len, d_slot_off, d_slot_beg, d_slot_end, site_cnt, site_start, site_partial, sites;
+    size_t bytes() const {
+        size_t b = 0;
+        for (const DevBuf *x : {&arr, &d_ref_len, &d_slot_off, &d_slot_beg, &d_slot_end, &site_cnt, &site_start, &site_partial, &sites}) b += x->cap;
+        return b;
+    }
+};
+
 struct plo_ctx {
     const plo_index *ix = nullptr;
     hipStream_t stream = nullptr;
@@ -1798,7 +1826,8 @@ struct plo_ctx {
     DevBuf bai_entry, bai_blk;
     HostBuf h_bai;
     hipEvent_t xev[2] = {nullptr, nullptr};
-    // plo_depth_add_dev: the plan word of every record and the call's two words (lowest offender << 4 | kind, n_counted); dpev: every plo_depth_* call
+    // plo_depth_add_dev: the plan word of every record and the call's two words (lowest offender << 4 | kind, n_counted); dpev: every plo_depth_* call.
+    // plo_pileup_add_dev and plo_pileup_sites_dev take the same scratch and events (a context runs one call at a time; the add's block holds n_events too)
     DevBuf dp_plan, dp_blk;
     HostBuf h_dp;
     hipEvent_t dpev[2] = {nullptr, nullptr};
@@ -4675,6 +4704,265 @@ plo_status plo_depth_reset(plo_ctx *c, plo_depth *dp) {
     if (dp->n_entries) HIP_TRY(c, hipMemsetAsync(dp->arr.p, 0, (size_t)dp->n_entries * 4, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     dp->finished.store(false);
+    return PLO_OK;
+}
+
+// ---- plo_pileup_* (pileup_core.hpp) -------------------------------------------------------------------------------------------------------------
+// the array, exactly its size, zeroed; the tables of the slots
+plo_status plo_pileup_create(plo_ctx *c, uint32_t n_ref, const int32_t *ref_len, const plo_pileup_opts *opts, plo_pileup **out) {
+    if (!c || !out || (n_ref && !ref_len) || (opts && opts->n_regions && !opts->regions)) return PLO_ERR_INVALID_ARG;
+    *out = nullptr;
+    c->err.clear();
+    if (n_ref > 0x7fffffffu) {
+        c->err = "plo_pileup_create: more than 2^31 - 1 references";
+        return PLO_ERR_RANGE;
+    }
+    static_assert(sizeof(plo_pileup_region) == sizeof(PileupRegion) && offsetof(plo_pileup_region, end) == offsetof(PileupRegion, end), "plo_pileup_region and PileupRegion are one layout");
+    plo_pileup *d = new plo_pileup();
+    d->device = c->ix->device;
+    d->n_ref = n_ref;
+    if (opts) d->exclude_flags = opts->exclude_flags;
+    d->ref_len.assign(ref_len, ref_len + n_ref);
+    d->slot_beg.resize((size_t)n_ref + 1);
+    d->slot_end.resize((size_t)n_ref + 1);
+    d->slot_off.resize((size_t)n_ref + 1);
+    uint32_t which = 0;
+    const int bad = pileup_layout(n_ref, d->ref_len.data(), opts ? opts->n_regions : 0u, opts ? (const PileupRegion *)opts->regions : nullptr, d->slot_beg.data(), d->slot_end.data(),
+                                  d->slot_off.data(), which);
+    if (bad) {
+        static const char *const what[] = {"", "is negative", "names a chromosome outside [0, n_ref)", "needs 0 <= beg <= end <= ref_len[ref_id]", "is the second region of its chromosome"};
+        c->err = std::string("plo_pileup_create: ") + (bad == 1 ? "ref_len[" : "regions[") + std::to_string(which) + "] " + what[bad];
+        delete d;
+        return PLO_ERR_INVALID_ARG;
+    }
+    d->n_bases = d->slot_off[n_ref];
+    if (hipSetDevice(c->ix->device) != hipSuccess) {
+        delete d;
+        c->err = "plo_pileup_create: hipSetDevice failed";
+        return PLO_ERR_HIP;
+    }
+    const size_t arr_bytes = std::max<size_t>((size_t)d->n_bases * 4 * PILEUP_CHANNELS, 32), tab = std::max<size_t>((size_t)n_ref * 4, 16);
+    hipError_t e = hipMalloc(&d->arr.p, arr_bytes);
+    if (e == hipSuccess) d->arr.cap = arr_bytes;
+    if (e == hipSuccess) e = d->d_ref_len.ensure(tab);
+    if (e == hipSuccess) e = d->d_slot_beg.ensure(tab);
+    if (e == hipSuccess) e = d->d_slot_end.ensure(tab);
+    if (e == hipSuccess) e = d->d_slot_off.ensure(((size_t)n_ref + 1) * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(d->arr.p, 0, arr_bytes, c->stream);
+    if (e == hipSuccess && n_ref) e = hipMemcpyAsync(d->d_ref_len.p, d->ref_len.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_ref) e = hipMemcpyAsync(d->d_slot_beg.p, d->slot_beg.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_ref) e = hipMemcpyAsync(d->d_slot_end.p, d->slot_end.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->d_slot_off.p, d->slot_off.data(), ((size_t)n_ref + 1) * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        c->err = std::string("plo_pileup_create: ") + hipGetErrorString(e) + " (" + std::to_string(arr_bytes) + " bytes for " + std::to_string(d->n_bases) + " bases)";
+        plo_pileup_destroy(d);
+        return e == hipErrorOutOfMemory ? PLO_ERR_OUT_OF_MEMORY : PLO_ERR_HIP;
+    }
+    *out = d;
+    return PLO_OK;
+}
+
+void plo_pileup_destroy(plo_pileup *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    for (DevBuf *b : {&d->arr, &d->d_ref_len, &d->d_slot_off, &d->d_slot_beg, &d->d_slot_end, &d->site_cnt, &d->site_start, &d->site_partial, &d->sites}) b->release();
+    delete d;
+}
+
+plo_status plo_pileup_info_get(const plo_pileup *d, plo_pileup_info *info) {
+    if (!d || !info) return PLO_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    info->array = d->arr.as<int32_t>();
+    info->n_bases = d->n_bases;
+    info->slot_off = d->slot_off.data();
+    info->slot_beg = d->slot_beg.data();
+    info->slot_end = d->slot_end.data();
+    info->bytes_allocated = d->bytes();
+    info->n_ref = d->n_ref;
+    info->exclude_flags = d->exclude_flags;
+    return PLO_OK;
+}
+
+// what every plo_pileup_* call on a context begins with: the object is of the context's device; with_ref: the context's index has the
+// object's chromosomes, with their bases
+static plo_status pileup_enter(plo_ctx *c, plo_pileup *d, bool with_ref, const char *name) {
+    c->err.clear();
+    if (d->device != c->ix->device) {
+        c->err = std::string(name) + ": the pileup object lives on device " + std::to_string(d->device) + ", the context on device " + std::to_string(c->ix->device);
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (with_ref) {
+        const DevIndex &ix = c->ix->d;
+        const std::vector<int> &cl = c->ix->host.chrom_len;
+        if (d->n_ref && (!ix.chrom_seq || !ix.chrom_len)) {
+            c->err = std::string(name) + ": the context's index has no chrom_seq";
+            return PLO_ERR_INVALID_ARG;
+        }
+        bool same = ix.n_chroms == d->n_ref && cl.size() == (size_t)d->n_ref;
+        for (uint32_t r = 0; same && r < d->n_ref; ++r) same = cl[r] == d->ref_len[r];
+        if (!same) {
+            c->err = std::string(name) + ": the chromosomes of the context's index (" + std::to_string(ix.n_chroms) + ") differ in number or length from the pileup object's (" + std::to_string(d->n_ref) + ")";
+            return PLO_ERR_INVALID_ARG;
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->ix->device));
+    for (int i = 0; i < 2; ++i)
+        if (!c->dpev[i]) HIP_TRY(c, hipEventCreate(&c->dpev[i]));
+    return PLO_OK;
+}
+
+plo_status plo_pileup_reset(plo_ctx *c, plo_pileup *pu) {
+    if (!c || !pu) return PLO_ERR_INVALID_ARG;
+    plo_status ps = pileup_enter(c, pu, false, "plo_pileup_reset");
+    if (ps != PLO_OK) return ps;
+    if (pu->n_bases) HIP_TRY(c, hipMemsetAsync(pu->arr.p, 0, (size_t)pu->n_bases * 4 * PILEUP_CHANNELS, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PLO_OK;
+}
+
+// The check and the add (pileup_core.hpp): two launches on the context's stream, a wave per record, at most 2048 workgroups of four waves;
+// the call's words come back behind them, one wait.  The add reads the check's word first.
+plo_status plo_pileup_add_dev(plo_ctx *c, plo_pileup *pu, const plo_depth_in *in, plo_pileup_add_out *out) {
+    if (!c || !pu || !in || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->err_record = UINT32_MAX;
+    plo_status ps = pileup_enter(c, pu, true, "plo_pileup_add_dev");
+    if (ps != PLO_OK) return ps;
+    const uint32_t n = in->n_records;
+    if (n && (!in->bytes || !in->record_off)) {
+        c->err = "plo_pileup_add_dev: the records and their offsets are required";
+        return PLO_ERR_INVALID_ARG;
+    }
+    if (n > DEPTH_MAX_RECORDS) {
+        c->err = "plo_pileup_add_dev: more than 2^27 - 1 records";
+        return PLO_ERR_RANGE;
+    }
+    if (!n) return PLO_OK;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->dp_plan.ensure((size_t)n * 8));
+    HIP_TRY(c, c->dp_blk.ensure(16));
+    HIP_TRY(c, c->h_dp.ensure(16));
+    DevPileup d;
+    memset(&d, 0, sizeof(d));
+    d.s.bytes = in->bytes;
+    d.s.n_bytes = in->n_bytes;
+    d.s.n = n;
+    d.s.record_off = in->record_off;
+    d.s.n_ref = pu->n_ref;
+    d.ref_len = pu->d_ref_len.as<int32_t>();
+    d.slot_off = pu->d_slot_off.as<uint64_t>();
+    d.slot_beg = pu->d_slot_beg.as<int32_t>();
+    d.slot_end = pu->d_slot_end.as<int32_t>();
+    d.arr = pu->arr.as<int32_t>();
+    d.exclude_flags = pu->exclude_flags;
+    d.chrom_seq = c->ix->d.chrom_seq;
+    d.plan = c->dp_plan.as<uint64_t>();
+    d.err = c->dp_blk.as<int>();
+    d.n_counted = c->dp_blk.as<unsigned>() + 1;
+    d.n_events = c->dp_blk.as<unsigned long long>() + 1;
+    uint32_t *h = c->h_dp.as<uint32_t>();
+    h[0] = (uint32_t)DEPTH_NO_RECORD;
+    h[1] = h[2] = h[3] = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->dp_blk.p, h, 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    const dim3 grid(std::min(2048u, (n + 3u) / 4u));
+    hipLaunchKernelGGL(k_pileup_check, grid, dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_pileup_add, grid, dim3(256), 0, st, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(h, c->dp_blk.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h[0] != (uint32_t)DEPTH_NO_RECORD) {
+        static const char *const what[] = {"", "record_off: it must start at 0, not decrease and end at n_bytes", "its length: fewer than the 36 bytes of block_size and the fixed fields",
+                                           "block_size: block_size + 4 differs from the record's length", "refID: outside [-1, n_ref)", "pos: outside [-1, 2^31 - 2]",
+                                           "its CIGAR: 36 + l_read_name + 4 n_cigar_op passes the record's end",
+                                           "its aux fields: the CIGAR is the placeholder <l_seq>S<n>N, and the fields begin behind the record's end, one in front of the first CG is malformed, or that CG leaves the record",
+                                           "its end: the record is counted and reaches beyond ref_len[refID]", "its bases and qualities: they pass the record's end",
+                                           "its read length: the record is counted and the M, I, S, =, X ops of its real CIGAR do not add up to l_seq"};
+        out->err_record = h[0] >> 4;
+        out->err_kind = h[0] & 15u;
+        c->err = "plo_pileup_add_dev: record " + std::to_string(out->err_record) + " is refused for " + (out->err_kind >= 1 && out->err_kind <= 10 ? what[out->err_kind] : "an unknown reason") +
+                 "; nothing was added";
+        return PLO_ERR_INVALID_ARG;
+    }
+    (void)hipEventElapsedTime(&out->add_ms, c->dpev[0], c->dpev[1]);
+    out->n_records = n;
+    out->n_counted = h[1];
+    out->n_events = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+    return PLO_OK;
+}
+
+// sites per tile, the 64-bit scan (records_core.hpp), the count comes down (the sites are sized by it), emit
+plo_status plo_pileup_sites_dev(plo_ctx *c, plo_pileup *pu, const plo_depth *dp, const plo_pileup_sites_opts *opts, plo_pileup_sites_out *out) {
+    if (!c || !pu || !out) return PLO_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    plo_status ps = pileup_enter(c, pu, true, "plo_pileup_sites_dev");
+    if (ps != PLO_OK) return ps;
+    static_assert(sizeof(plo_pileup_site) == sizeof(PileupSite) && offsetof(plo_pileup_site, count) == offsetof(PileupSite, count), "plo_pileup_site and PileupSite are one layout");
+    plo_pileup_sites_opts o = {PLO_PILEUP_MASK_DEFAULT, 1, 0, 1};
+    if (opts) o = *opts;
+    if (dp && dp->device != pu->device) {
+        c->err = "plo_pileup_sites_dev: the depth object lives on another device";
+        return PLO_ERR_INVALID_ARG;
+    }
+    const int bad = pileup_sites_refused(o.min_count, o.frac_num, o.frac_den, dp != nullptr, dp && dp->finished.load(), dp && dp->n_ref == pu->n_ref && dp->ref_len == pu->ref_len);
+    if (bad) {
+        static const char *const what[] = {"", "min_count must be 1 or more", "frac_den is 0 while frac_num is not", "the depth object is not finished (plo_depth_finish_dev)",
+                                           "the depth object was made over another list of chromosomes"};
+        c->err = std::string("plo_pileup_sites_dev: ") + what[bad];
+        return PLO_ERR_INVALID_ARG;
+    }
+    hipStream_t st = c->stream;
+    const unsigned long long n_tiles = (pu->n_bases + PILEUP_TILE - 1) / PILEUP_TILE;
+    if (!n_tiles) return PLO_OK;
+    if (n_tiles > 0xffffffffull) {
+        c->err = "plo_pileup_sites_dev: more than 2^32 - 1 tiles";
+        return PLO_ERR_RANGE;
+    }
+    const uint32_t nt = (uint32_t)n_tiles, nb = (nt + REC_SCAN_CHUNK - 1) / REC_SCAN_CHUNK;
+    HIP_TRY(c, pu->site_cnt.ensure((size_t)nt * 8));
+    HIP_TRY(c, pu->site_start.ensure(((size_t)nt + 1) * 8));
+    HIP_TRY(c, pu->site_partial.ensure((size_t)nb * 8));
+    HIP_TRY(c, c->h_dp.ensure(16));
+    DevPileupSites d;
+    memset(&d, 0, sizeof(d));
+    d.arr = pu->arr.as<int32_t>();
+    d.slot_off = pu->d_slot_off.as<uint64_t>();
+    d.slot_beg = pu->d_slot_beg.as<int32_t>();
+    d.n_ref = pu->n_ref;
+    d.n_bases = pu->n_bases;
+    d.depth = dp ? dp->arr.as<int32_t>() : nullptr;
+    d.depth_slot_off = dp ? dp->d_slot_off.as<uint64_t>() : nullptr;
+    d.chrom_seq = c->ix->d.chrom_seq;
+    d.channel_mask = o.channel_mask;
+    d.min_count = o.min_count;
+    d.frac_num = o.frac_num;
+    d.frac_den = o.frac_den;
+    d.cnt = pu->site_cnt.as<unsigned long long>();
+    d.start = pu->site_start.as<unsigned long long>();
+    unsigned long long *start = pu->site_start.as<unsigned long long>();
+    const dim3 grid((nt + 3u) / 4u);
+    HIP_TRY(c, hipEventRecord(c->dpev[0], st));
+    hipLaunchKernelGGL(k_pileup_sites<false>, grid, dim3(256), 0, st, d, n_tiles);
+    hipLaunchKernelGGL(k_rec_scan_sums, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, pu->site_partial.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rec_scan_partials, dim3(1), dim3(64), 0, st, pu->site_partial.as<unsigned long long>(), nt, nb, start);
+    hipLaunchKernelGGL(k_rec_scan_apply, dim3(nb, 1), dim3(64), 0, st, (const unsigned long long *)d.cnt, nt, nb, (const unsigned long long *)pu->site_partial.as<unsigned long long>(), start);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *h = c->h_dp.as<unsigned long long>();
+    HIP_TRY(c, hipMemcpyAsync(h, start + nt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const unsigned long long n_sites = h[0];
+    HIP_TRY(c, pu->sites.ensure(std::max<size_t>((size_t)n_sites * sizeof(PileupSite), 16)));
+    d.site = pu->sites.as<PileupSite>();
+    hipLaunchKernelGGL(k_pileup_sites<true>, grid, dim3(256), 0, st, d, n_tiles);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->dpev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&out->sites_ms, c->dpev[0], c->dpev[1]);
+    out->site = pu->sites.as<plo_pileup_site>();
+    out->n_sites = n_sites;
     return PLO_OK;
 }
 

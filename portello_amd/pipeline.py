@@ -80,6 +80,8 @@ class PipelineStats:
     run_groups: List[int] = field(default_factory=list)  # sorted_runs: the windows with records in every written run, in out_paths order (all 1 with run_windows=1)
     depth_device_ms: float = 0.0  # depth_out: HIP-event time of plo_depth_add_dev over the windows, plus the finish, the windows and the runs
     depth_paths: List[str] = field(default_factory=list)  # depth_out: <prefix>.per-base.bed and <prefix>.regions.bed
+    pileup_device_ms: float = 0.0  # pileup_out: HIP-event time of plo_pileup_add_dev over the windows and of the sites call (without depth_out: and of the depth calls made for it)
+    pileup_paths: List[str] = field(default_factory=list)  # pileup_out: <prefix>.sites.tsv
     sort_device_ms: float = 0.0  # sorted_runs: HIP-event time of plo_records_sort_dev (check + keys + tile sort, merges, offsets, permuted copy)
     finish_device_ms: float = 0.0  # device_finish: HIP-event time of the finishing, reverse-complement and SA-text kernels
     stage_done_s: dict = field(default_factory=dict)  # when each stage's thread ended, and the closes behind them (seconds after the start)
@@ -97,8 +99,18 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                    out_shards: int = 1, n_readers: int = 1, device_records: bool = False, device_bgzf: bool = False, device_batch: bool = False,
                    device_input: bool = False, emit_nm: bool = False, emit_md: bool = False, sorted_runs: bool = False,
                    index_runs: bool = False, emit_eqx: bool = False, run_windows: int = 1, run_budget_bytes: Optional[int] = None,
-                   run_chunk_bytes: int = 1 << 30, depth_out: Optional[str] = None, depth_window: int = 500, depth_deletions: bool = False) -> PipelineStats:  # noqa: E501
-    """depth_out (default None; a path prefix; needs device_records=True): the depth of the output records is taken while they lie on the
+                   run_chunk_bytes: int = 1 << 30, depth_out: Optional[str] = None, depth_window: int = 500, depth_deletions: bool = False,
+                   pileup_out: Optional[str] = None, pileup_min_count: int = 2, pileup_min_frac: Sequence[int] = (1, 5),
+                   pileup_regions: Optional[Sequence[Sequence[int]]] = None) -> PipelineStats:  # noqa: E501
+    """pileup_out (default None; a path prefix; needs device_records=True): the allele pileup of the output records against the index's
+    chrom_seq, taken while the records lie on the device.  The process holds ONE pileup object (pileup.DevicePileup over ref_lens, or over
+    pileup_regions = [(ref_id, beg, end)], at most one a chromosome: 32 bytes a base), made by the first lift worker; every worker adds its
+    window's plo_records_out right behind plo_records_build_dev (plo_pileup_add_dev: integer atomics, so neither the order of the windows
+    nor the number of workers changes a value).  When the workers are joined the main thread's context lists the candidate sites -- a base
+    whose largest counter among A C G T DEL INS is at least pileup_min_count and at least pileup_min_frac = (num, den) of the depth -- and
+    writes <prefix>.sites.tsv (pileup.write_sites).  The depth is the run's depth object; without depth_out one is made for the purpose and
+    no beds are written.  PipelineStats: pileup_device_ms, pileup_paths.  With pileup_out=None every byte of every output is what it was.
+    depth_out (default None; a path prefix; needs device_records=True): the depth of the output records is taken while they lie on the
     device, so that no mosdepth or `samtools depth` pass has to read the written file back.  The process holds ONE depth object
     (depth.DeviceDepth over ref_lens: 4 bytes a reference base); every lift worker adds its window's plo_records_out right behind
     plo_records_build_dev (plo_depth_add_dev on the worker's own context and stream: the adds are integer atomics, so neither the order of
@@ -202,6 +214,10 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
     run_windows = int(run_windows)
     if depth_out is not None and not device_records:
         raise ValueError("depth_out adds the records plo_records_build_dev leaves on the device: it needs device_records=True")
+    if pileup_out is not None and not device_records:
+        raise ValueError("pileup_out adds the records plo_records_build_dev leaves on the device: it needs device_records=True")
+    if pileup_out is not None and (int(pileup_min_count) < 1 or len(pileup_min_frac) != 2 or (int(pileup_min_frac[0]) != 0 and int(pileup_min_frac[1]) == 0)):
+        raise ValueError("pileup_min_count must be 1 or more and pileup_min_frac a pair (num, den) with den != 0 unless num == 0")
     if depth_out is not None and int(depth_window) < 1:
         raise ValueError("depth_window is the size of the windows of <prefix>.regions.bed in bases: it must be 1 or more")
     if run_windows != 1 and not sorted_runs:
@@ -302,6 +318,17 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
             if depth_box[0] is None:
                 depth_box[0] = _depth.DeviceDepth(eng, ref_lens, count_deletions=depth_deletions)
             return depth_box[0]
+
+    want_depth = depth_out is not None or pileup_out is not None  # the sites are tested against the depth
+    pileup_box = [None]  # pileup_out: the process's one pileup object, made by the first lift worker that has a context
+
+    def pileup_object(eng):
+        from . import pileup as _pileup
+
+        with depth_lock:
+            if pileup_box[0] is None:
+                pileup_box[0] = _pileup.DevicePileup(eng, ref_lens, regions=pileup_regions)
+            return pileup_box[0]
 
     merge_windows = sorted_runs and run_windows != 1
     if merge_windows:
@@ -537,9 +564,13 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             ro = eng.records_build_dev(ddesc, up.records_in(labels, is_target_region))
                             marks.append(("records", time.perf_counter()))
                             depth_ms = 0.0
-                            if depth_out is not None and ro.n_records:
+                            if want_depth and ro.n_records:
                                 depth_ms = float(depth_object(eng).add(eng, ro.bytes, ro.n_bytes, ro.n_records, ro.record_off).add_ms)
                                 marks.append(("depth", time.perf_counter()))
+                            pileup_ms = 0.0
+                            if pileup_out is not None and ro.n_records:
+                                pileup_ms = float(pileup_object(eng).add(ro, eng).add_ms)
+                                marks.append(("pileup", time.perf_counter()))
                             srt, sort_ms = None, 0.0
                             if sorted_runs and ro.n_records:
                                 srt = eng.records_sort_dev(ro.bytes, ro.n_bytes, ro.n_records, ro.record_off, len(ref_names))
@@ -573,7 +604,11 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
                             st.md_device_ms += md_ms
                             st.eqx_device_ms += eqx_ms
                             st.sort_device_ms += sort_ms
-                            st.depth_device_ms += depth_ms
+                            if depth_out is not None:
+                                st.depth_device_ms += depth_ms
+                            else:
+                                pileup_ms += depth_ms
+                            st.pileup_device_ms += pileup_ms
                             st.index_device_ms += index_ms
                             st.batch_device_ms += getattr(up, "batch_ms", 0.0)
                             st.bgzf_device_ms += getattr(rb, "bgzf_ms", 0.0)
@@ -697,30 +732,42 @@ def run_bam_to_bam(in_path: str, out_path: str, index: api.Index, index_data: ab
         t_merger.start()
     for t in front:
         t.join()
-    if depth_out is not None and not st.errors:  # every add is through: the workers are joined
+    if want_depth and not st.errors:  # every add is through: the workers are joined
         from . import depth as _depth
+        from . import pileup as _pileup
 
         deng = None
         try:
             deng = api.Engine(index)
             dobj = depth_object(deng)
             ms = dobj.finish(deng)
-            win_first, win_sums, wms = dobj.windows(deng, int(depth_window))
-            runs_, rms = dobj.runs(deng, with_ms=True)
-            st.depth_device_ms += ms + wms + rms
-            st.depth_paths = [depth_out + ".per-base.bed", depth_out + ".regions.bed"]
-            _depth.write_per_base(st.depth_paths[0], ref_names, runs_)
-            _depth.write_regions(st.depth_paths[1], ref_names, [int(n) for n in ref_lens], int(depth_window), win_first, win_sums)
+            if depth_out is not None:
+                win_first, win_sums, wms = dobj.windows(deng, int(depth_window))
+                runs_, rms = dobj.runs(deng, with_ms=True)
+                st.depth_device_ms += ms + wms + rms
+                st.depth_paths = [depth_out + ".per-base.bed", depth_out + ".regions.bed"]
+                _depth.write_per_base(st.depth_paths[0], ref_names, runs_)
+                _depth.write_regions(st.depth_paths[1], ref_names, [int(n) for n in ref_lens], int(depth_window), win_first, win_sums)
+            else:
+                st.pileup_device_ms += ms
+            if pileup_out is not None:
+                sites_, sms = pileup_object(deng).sites(dobj, min_count=int(pileup_min_count), min_frac=(int(pileup_min_frac[0]), int(pileup_min_frac[1])), engine=deng, with_ms=True)
+                st.pileup_device_ms += sms
+                st.pileup_paths = [pileup_out + ".sites.tsv"]
+                _pileup.write_sites(st.pileup_paths[0], ref_names, sites_)
         except BaseException as e:  # noqa: BLE001
-            st.errors.append(f"depth: {e!r}")
+            st.errors.append(f"{'depth' if pileup_out is None else 'depth / pileup'}: {e!r}")
             abort.set()
         finally:
-            if depth_box[0] is not None:
-                depth_box[0].close()
+            for box in (depth_box, pileup_box):
+                if box[0] is not None:
+                    box[0].close()
             if deng is not None:
                 deng.close()
-    elif depth_box[0] is not None:
-        depth_box[0].close()
+    else:
+        for box in (depth_box, pileup_box):
+            if box[0] is not None:
+                box[0].close()
     if merge_windows:
         with mcond:
             for ci in range(len(rds)):

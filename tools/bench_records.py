@@ -36,6 +36,9 @@ For a chr20 window of --reads reads held in memory, JSON with
   - plo_depth_add_dev on the window's records (--depth-out; this leg runs alone): add_ms beside index_ms of the same records (the same walk
     of every CIGAR without atomics), and finish_ms, windows_ms and runs_ms beside one device-to-device hipMemcpyAsync of the array's bytes
     taken in the same process; differences, depths, window sums and the run count are compared with numpy's before anything is timed
+  - plo_pileup_add_dev on the window's records (--pileup-out; this leg runs alone): add_ms beside nm_ms of the same window (the same base
+    pairs, no scattered atomics) and depth's add_ms on the same records, sites_ms beside one device-to-device copy of the array's bytes;
+    events per record and their share by channel; the array and the sites are compared with numpy's (tests/pileup_expect.py) first
   - plo_bgzf_inflate_dev + plo_window_cut_dev on the window's file (--cut-out; this leg runs alone): inflate_ms and cut_ms (HIP events) and
     the calls' wall time beside the wall time of bam.BamReader.read_window + devbatch.upload_records on the same file; read_rec_off, the
     window's bytes and the unmapped records are compared with the host reader's before anything is timed.  With --e2e-reads also
@@ -53,6 +56,7 @@ Exits non-zero on any byte mismatch between the device's records and the host's.
     python tools/bench_records.py --reads 50000 --index-out profiles/r15_index_window.json
     python tools/bench_records.py --reads 50000 --merge-out profiles/r18_merge_runs.json --merge-windows 4
     python tools/bench_records.py --reads 50000 --depth-out profiles/r19_depth.json
+    python tools/bench_records.py --reads 50000 --pileup-out profiles/r20_pileup.json
 """
 import argparse
 import ctypes as C
@@ -1027,6 +1031,96 @@ def depth_leg(a, win, index, cn, rn, rl, dev):
     return res, bool(same)
 
 
+def pileup_leg(a, win, index, cn, rn, chrom_seq, dev):
+    """ONE window: plo_pileup_add_dev on the window's records beside plo_nm_dev on the same window (the same base pairs walked, no scattered
+    atomics) and plo_depth_add_dev on the same records; plo_pileup_sites_dev beside a device-to-device copy of the array's bytes.  Before
+    anything is timed the array and the sites are compared with numpy's (tests/pileup_expect.py, counts_numpy): every non-zero base of the
+    array comes down as a site of the mask 0xFF, and the array's sum and its count of non-zero counters are taken on the device"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import pileup_expect as px
+
+    from portello_amd import abi, api, depth, devbatch, pileup
+    from portello_amd.gather import device_view
+
+    eng = api.Engine(index)
+    b, f, r = win.batch_raw()
+    up = devbatch.upload_raw_window(b, f, r, dev)
+    torch.cuda.synchronize()
+    ddesc = up.batch.desc()
+    sa_in, keep = devbatch.sa_inputs(rn, dev)
+    labels = devbatch.contig_labels(cn, dev)
+    rin = up.records_in(labels, False)
+    out = eng.liftover_batch_dev(ddesc)
+    eng.compact_output_dev(out)
+    eng.finish_batch_dev(ddesc, up.finish_in())
+    eng.sa_segments_dev(sa_in)
+    ro = eng.records_build_dev(ddesc, rin)
+    n, nb, n_ref = int(ro.n_records), int(ro.n_bytes), len(rn)
+    chroms = [x.cpu().numpy() for x in chrom_seq]
+    rl = [len(c) for c in chroms]
+
+    def down(ptr, count, dtype):
+        return device_view(ptr, count * np.dtype(dtype).itemsize, torch.uint8, dev).cpu().numpy().view(dtype) if count else np.zeros(0, dtype)
+
+    data, off = down(ro.bytes, nb, np.uint8), down(ro.record_off, n + 1, np.uint64).astype(np.int64)
+    keys, counts, n_counted, n_events, per_channel = px.counts_numpy(data, off, chroms)
+    obj = pileup.DevicePileup(eng, rl)
+    dobj = depth.DeviceDepth(eng, rl)
+    info = obj.info()
+    n_bases = int(info.n_bases)
+    ao = obj.add(ro, eng)
+    same = (int(ao.n_counted), int(ao.n_events)) == (n_counted, n_events)
+    arr = device_view(info.array, 32 * n_bases, torch.uint8, dev).view(torch.int32)
+    same = same and int(arr.sum(dtype=torch.int64)) == n_events and int(torch.count_nonzero(arr)) == len(keys)
+    every = obj.sites(channel_mask=0xFF, engine=eng)  # every base with a non-zero counter
+    got = ((every["ref_id"].astype(np.int64)[:, None] << 40) | (every["pos"].astype(np.int64)[:, None] << 3) | np.arange(8)[None, :])[every["count"] != 0]
+    same = same and np.array_equal(got, keys) and np.array_equal(every["count"][every["count"] != 0], counts)
+    same = same and all(int(s["ref_base"]) == int(chroms[int(s["ref_id"])][int(s["pos"])]) for s in every[::max(1, len(every) // 1000)])
+    dobj.add(eng, ro.bytes, nb, n, ro.record_off)
+    dobj.finish(eng)
+    sites = obj.sites(dobj, min_count=2, min_frac=(1, 5), engine=eng)
+    add_ms, nm_ms, depth_ms, sites_ms = [], [], [], []
+    for k in range(a.warmup + a.reps):
+        obj.reset(eng)
+        dobj.reset(eng)
+        ao = obj.add(ro, eng)
+        do = dobj.add(eng, ro.bytes, nb, n, ro.record_off)
+        no = eng.nm_dev(ddesc)
+        dobj.finish(eng)
+        so = obj.sites_dev(dobj, min_count=2, min_frac=(1, 5), engine=eng)
+        if k >= a.warmup:
+            add_ms.append(float(ao.add_ms))
+            depth_ms.append(float(do.add_ms))
+            nm_ms.append(float(no.nm_ms))
+            sites_ms.append(float(so.sites_ms))
+    same = same and int(so.n_sites) == len(sites)
+    bytes_allocated = int(obj.info().bytes_allocated)
+    obj.close()
+    dobj.close()
+    src, dst = torch.zeros(max(16, 32 * n_bases), dtype=torch.uint8, device=dev), torch.empty(max(16, 32 * n_bases), dtype=torch.uint8, device=dev)
+    d2d = []
+    for k in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            d2d.append(e0.elapsed_time(e1))
+    eng.close()
+    res = {"leg": "pileup", "reads": win.n_records, "n_records": n, "n_counted": n_counted, "n_events": n_events, "events_per_record": n_events / max(1, n_counted),
+           "event_share_by_channel": {name: per_channel[k] / max(1, n_events) for k, name in enumerate(abi.PILEUP_CHANNEL_NAMES)}, "n_ref": n_ref, "array_bases": n_bases,
+           "array_bytes": 32 * n_bases, "bytes_allocated": bytes_allocated, "bases_with_an_event": int(len(every)), "n_sites_min2_frac_1_5": int(len(sites)), "matches_numpy": bool(same),
+           "add_ms": stats(add_ms), "nm_ms_same_window": stats(nm_ms), "depth_add_ms_same_records": stats(depth_ms), "sites_ms": stats(sites_ms), "d2d_copy_of_array_ms": stats(d2d),
+           "note": "add_ms: check + add kernels (HIP events); nm_ms: plo_nm_dev, the same base pairs without scattered atomics; the copy moves array_bytes in and out, the sites "
+                   "call reads array_bytes twice (count, emit) and 4 bytes a base of the depth array",
+           "not_measured": ["a whole-genome array (99 GB)", "deep pile-ups on one cache line (many reads mismatching at one base)", "adds of several contexts timed together"]}
+    return res, bool(same)
+
+
 def abi_entry_dtype():
     from portello_amd import abi
 
@@ -1055,6 +1149,7 @@ def main():
     ap.add_argument("--index-out", default="", help="run the index leg (plo_records_index_dev on the window's sorted records, against the host's entries and a device-to-device copy of its algorithmic bytes; the writer's and the merge's index on the CPU) alone and write its JSON there")
     ap.add_argument("--merge-out", default="", help="run the merge leg (--merge-windows windows sorted and retained on the device; plo_runs_merge_plan_dev and the summed plo_runs_merge_emit_dev against plo_records_sort_dev over their concatenation and a device-to-device copy of the same bytes) alone and write its JSON there")
     ap.add_argument("--depth-out", default="", help="run the depth leg (plo_depth_add_dev beside plo_records_index_dev on the same records; finish, windows and runs beside a device-to-device copy of the array) alone and write its JSON there")
+    ap.add_argument("--pileup-out", default="", help="run the pileup leg (plo_pileup_add_dev beside plo_nm_dev on the same window and plo_depth_add_dev on the same records; plo_pileup_sites_dev beside a device-to-device copy of the array) alone and write its JSON there")
     ap.add_argument("--depth-window", type=int, default=500, help="window size of the depth leg")
     ap.add_argument("--depth-deletions", action="store_true", help="the depth leg counts D as covered")
     ap.add_argument("--merge-windows", type=int, default=4, help="windows of the merge leg: --reads is cut into that many")
@@ -1108,6 +1203,15 @@ def main():
             with open(a.cut_out, "w") as fh:
                 fh.write(json.dumps(cres, indent=1) + "\n")
         print(json.dumps(cres))
+        sys.exit(0 if ok else 1)
+    if a.pileup_out:
+        pres, ok = pileup_leg(a, win, index, cn, rn, w.chrom_seq, dev)
+        win.close()
+        rd.close()
+        os.makedirs(os.path.dirname(os.path.abspath(a.pileup_out)), exist_ok=True)
+        with open(a.pileup_out, "w") as fh:
+            fh.write(json.dumps(pres, indent=1) + "\n")
+        print(json.dumps(pres))
         sys.exit(0 if ok else 1)
     if a.depth_out:
         dres, ok = depth_leg(a, win, index, cn, rn, [int(x.numel()) for x in w.chrom_seq], dev)
