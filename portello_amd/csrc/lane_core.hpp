@@ -548,6 +548,22 @@ constexpr int LANE_KVS_DWORDS = 2 * LANE_KVS;  // behind the wave's slice (lds +
 // of a sort window wider than 128 reads are every n-th read of a longer stretch of the contig, and their union of block-map entries grows
 // with the window (wgs30x, 4.8-fold coverage per haplotype: ~0.15 entries per kb, 64 neighbouring reads span 200 kb, 512 span 1.6 Mb).
 constexpr int LANE_KVS_MAX = 512;
+#ifdef PLO_EMULATOR
+// Test visibility (tests/emu/, emulator builds only -- no device code sees this): how the liftover loops of lane_tile and of the streaming
+// kernel (lane_stream.hpp) were entered and where their block-map entries came from, summed until the harness clears them.
+struct EmuKvStats {
+    unsigned long long all_lds;     // lane_tile rounds that ran the all-staged copy of the liftover loop
+    unsigned long long mixed;       // ... the copy with the global fallback
+    unsigned long long global_kv;   // block-map entries lane_tile's cursors fetched from global memory (per lane)
+    unsigned long long s_restage;   // streaming kernel: stagings of the team's entries
+    unsigned long long s_mid;       // ... of them while another lane was in the middle of an item
+    unsigned long long s_flip_on;   // ... lanes in the middle of an item whose kv_lds went from false to true
+    unsigned long long s_flip_off;  // ... and from true to false
+    unsigned long long s_global_kv; // streaming kernel: entries fetched from global memory (per lane)
+};
+inline EmuKvStats g_emu_kv = {0, 0, 0, 0, 0, 0, 0, 0};
+constexpr unsigned EMU_LIFT_TRIPS = 1u << 18;  // trips of one group's liftover loop before the emulator gives up (an item of 2^16 ops and keys)
+#endif
 // NOSHIFT: an instantiation for groups of the class without the shift stage (forward-mapped contig segments), compiled without that
 // stage's code and state -- lanes that would need it are handed to the retry list (the class order keeps them away).
 // STATS: the launch counts its algorithmic bytes (SURVEY.md 8(d)'s B_item per item: plo_timing::algo_bytes) and the lanes at work per
@@ -1194,6 +1210,9 @@ PLO_DEV void lane_tile(const DevIndex &ix, const DevBatch &bt, const DevWork &wk
                                 const KV e = ix.kv[idx];
                                 key = e.key;
                                 val = e.val;
+#ifdef PLO_EMULATOR
+                                g_emu_kv.global_kv += 1;
+#endif
                             }
                         }
                     }
@@ -1201,8 +1220,19 @@ PLO_DEV void lane_tile(const DevIndex &ix, const DevBatch &bt, const DevWork &wk
                 kv_fetch(lo_on & (W0 < kv1), W0, kn, vn);
                 kv_fetch(lo_on & (W0 + 1 < kv1), W0 + 1, kf, vf);
                 PLO_MARK("LIFTOVER LOOP BEGIN");
+#ifdef PLO_EMULATOR
+                unsigned emu_trips = 0;
+#endif
                 for (unsigned long long bm; (bm = wv::ballot(lo_on & ((k < n) | in_op))) != 0ull;) {
                     PLO_LC(7, 1)
+#ifdef PLO_EMULATOR
+                    // a walk that does not end (tests/emu/: a wrong comparison in this loop) is reported, not waited for: every trip emits or
+                    // consumes something, so a group is through long before EMU_LIFT_TRIPS; the harness answers 2 (CNT_ERROR)
+                    if (++emu_trips > EMU_LIFT_TRIPS) {
+                        if (lane == 0) wv::atomic_add_global(&wk.counters[CNT_ERROR], 1ull);
+                        break;
+                    }
+#endif
                     if constexpr (STATS) {
                         ctx.u_act += (unsigned)__builtin_popcountll(bm);
                         ctx.u_trips += 1;
@@ -1263,6 +1293,12 @@ PLO_DEV void lane_tile(const DevIndex &ix, const DevBatch &bt, const DevWork &wk
                     vf = adv ? fv : vf;
                 }
             };
+#ifdef PLO_EMULATOR
+            {
+                const bool any_on = wv::ballot(lo_on) != 0ull, any_out = wv::ballot(lo_on & !kv_lds) != 0ull;
+                if (lane == 0 && kvs != nullptr && any_on) (any_out ? g_emu_kv.mixed : g_emu_kv.all_lds) += 1;
+            }
+#endif
             if (kvs != nullptr && wv::ballot(lo_on & !kv_lds) == 0ull) run(std::true_type{});
             else run(std::false_type{});
             PLO_MARK("LIFTOVER LOOP END");

@@ -586,6 +586,9 @@ PLO_DEV void pipe_stage_liftover(const DevIndex &ix, const DevBatch &bt, const D
                 const KV e = ix.kv[idx];
                 key = e.key;
                 val = e.val;
+#ifdef PLO_EMULATOR
+                g_emu_kv.s_global_kv += 1;
+#endif
             }
         }
     };
@@ -668,7 +671,20 @@ PLO_DEV void pipe_stage_liftover(const DevIndex &ix, const DevBatch &bt, const D
                     kvs_base = -wv::reduce_max(live ? -W0 : -IMAX);
                     const int top = wv::reduce_max(live ? need_hi : 0);
                     kvs_cnt = wv::imax(0, wv::imin(top - kvs_base, LANE_KVS));
+#ifdef PLO_EMULATOR
+                    const bool emu_was_lds = kv_lds;
+#endif
                     kv_lds = live & (need_hi <= kvs_base + kvs_cnt);
+#ifdef PLO_EMULATOR
+                    {
+                        const bool mid = live & !mine;
+                        if (lane == 0) g_emu_kv.s_restage += 1;
+                        const bool any_mid = wv::ballot(mid) != 0ull;
+                        if (lane == 0 && any_mid) g_emu_kv.s_mid += 1;
+                        if (mid & !emu_was_lds & kv_lds) g_emu_kv.s_flip_on += 1;
+                        if (mid & emu_was_lds & !kv_lds) g_emu_kv.s_flip_off += 1;
+                    }
+#endif
                     KV e0 = {0, 0}, e1 = {0, 0};
                     if (lane < kvs_cnt) e0 = ix.kv[kvs_base + lane];
                     if (lane + 64 < kvs_cnt) e1 = ix.kv[kvs_base + lane + 64];

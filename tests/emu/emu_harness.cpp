@@ -43,6 +43,7 @@ extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in 
         fprintf(stderr, "emu: pack_index failed: %s\n", err.c_str());
         return 1;
     }
+    pk.kv.shrink_to_fit();  // (the sanitizer programs: the entry behind the last map's last key is not the vector's)
     DevIndex ix;
     ix.kv = pk.kv.data();
     ix.cs_kv_off = pk.cs_kv_off.data();
@@ -199,9 +200,15 @@ extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in 
     total_ops = all_ops;
 
     uint64_t out_cap = 4 * total_ops + 64ull * n_items + 1024 + 8 * SLAB_OPS;
+    {   // the descriptors as build_item_desc stored them, for emu_last_windows
+        extern std::vector<uint32_t> g_last_desc[6];
+        const std::vector<uint32_t> *src[6] = {&d_w0, &d_w1, &d_kv0, &d_kv1, &item_cls, &item_region};
+        for (int k = 0; k < 6; ++k) g_last_desc[k].assign(src[k]->begin(), src[k]->begin() + n_items);
+    }
     for (int attempt = 0; attempt < 6; ++attempt) {
         o->cigar.assign(out_cap, 0);
         memset(counters, 0, sizeof(counters));
+        g_emu_kv = EmuKvStats{0, 0, 0, 0, 0, 0, 0, 0};
         wk.out_cigar = o->cigar.data();
         wk.out_cap = out_cap;
         std::vector<unsigned char> lds(tile_mem_bytes(cap) + 64);
@@ -435,6 +442,22 @@ extern "C" int emu_liftover_batch(const plo_index_desc *ixd, const plo_batch_in 
 }
 
 void *g_last_emu_out = nullptr;
+std::vector<uint32_t> g_last_desc[6];
+
+// the staging counters of the last emu_liftover_batch call (EmuKvStats, lane_core.hpp), in the struct's order
+extern "C" void emu_kv_stats(unsigned long long *out /*[8]*/) {
+    const unsigned long long v[8] = {g_emu_kv.all_lds, g_emu_kv.mixed, g_emu_kv.global_kv, g_emu_kv.s_restage, g_emu_kv.s_mid, g_emu_kv.s_flip_on, g_emu_kv.s_flip_off, g_emu_kv.s_global_kv};
+    memcpy(out, v, sizeof(v));
+}
+
+// what build_item_desc stored for the items of the last emu_liftover_batch call, item order: out[0 .. 6) = w0, w1, kv0, kv1, class, region
+// dwords, `cap` values each.  Returns the number of items.
+extern "C" uint32_t emu_last_windows(uint32_t *const *out, uint32_t cap) {
+    const uint32_t n = (uint32_t)g_last_desc[0].size();
+    for (int k = 0; k < 6; ++k)
+        for (uint32_t i = 0; i < n && i < cap; ++i) out[k][i] = g_last_desc[k][i];
+    return n;
+}
 
 extern "C" void emu_free_last() {
     delete (Out *)g_last_emu_out;

@@ -15,7 +15,7 @@ _ASAN = os.path.join(_HERE, "emu", "emu_enumerate_asan")
 
 
 def _sources():
-    return [os.path.join(_HERE, "emu", f) for f in ("emu_enumerate.cpp", "emu_harness.cpp", "plo_wave.hpp", "emu_inflate.hpp", "emu_finish.hpp")] + [
+    return [os.path.join(_HERE, "emu", f) for f in ("emu_enumerate.cpp", "emu_harness.cpp", "emu_batch_file.hpp", "plo_wave.hpp", "emu_inflate.hpp", "emu_finish.hpp")] + [
         os.path.join(ROOT, "portello_amd", "csrc", f) for f in ("lift_core.hpp", "lane_core.hpp", "lane_stream.hpp", "inflate.hpp", "finish_core.hpp",
                                                                "lift_types.hpp", "index_pack.hpp", "enumerate.hpp")]
 
@@ -60,9 +60,10 @@ def encode(index: abi.IndexData, cases, lane_max_w: int) -> bytes:
     return b"".join(parts)
 
 
-def decode(data: bytes, n_cases: int):
+def decode(data: bytes, n_cases: int, n_modes=2):
     """-> per case [(rc, lane items, abi.BatchResult) for the lane-per-item run and for the scan formulation]; rc as emu_liftover_batch
-    returns it (3: lifted, but an item has a negative rev_pos and the card refuses the batch)"""
+    returns it (3: lifted, but an item has a negative rev_pos and the card refuses the batch).  (n_modes: the runs per case, one number or a
+    number per case: emu_liftover_lib's program writes this format too.)"""
     at = 0
 
     def take(dt, n):
@@ -72,9 +73,9 @@ def decode(data: bytes, n_cases: int):
         return a
 
     out = []
-    for _ in range(n_cases):
+    for k in range(n_cases):
         modes = []
-        for _m in range(2):
+        for _m in range(n_modes if isinstance(n_modes, int) else n_modes[k]):
             rc, n, lanes = (int(x) for x in take(np.uint32, 3))
             seg, cseg = take(np.uint32, n), take(np.uint32, n)
             st, fl, mq = take(np.uint8, n), take(np.uint8, n), take(np.uint8, n)

@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 _LIB = os.path.join(_HERE, "emu", "libplo_emu.so")
 _lib = None
+CNT_NRETRY = 7        # counters[] of liftover_batch: items the lane code handed to the retry list (lift_types.hpp)
+CNT_LANE_ITEMS = 23   # ... and the items that took the lane-per-item path (the harness stores it there)
 
 
 def build(force=False, sanitize=False):
@@ -137,3 +139,29 @@ def xor_windows(ref: np.ndarray, r0: int, seq: np.ndarray, seq_off: int, read_le
     L.emu_xor_windows(ref.ctypes.data, len(ref), r0, seq.ctypes.data, seq.nbytes, seq_off, read_len, seq_fmt, int(flip), q0,
                       out.ctypes.data_as(C.POINTER(C.c_uint8)), ok.ctypes.data_as(C.POINTER(C.c_int)))
     return out.reshape(3, 16), ok
+
+
+KV_STATS = ("all_lds", "mixed", "global_kv", "s_restage", "s_mid", "s_flip_on", "s_flip_off", "s_global_kv")
+
+
+def kv_stats() -> dict:
+    """the staging counters of the last liftover_batch call (EmuKvStats, lane_core.hpp): rounds of lane_tile through the all-staged and the
+    mixed copy of the liftover loop, block-map entries fetched from global memory, and the streaming kernel's stagings"""
+    L = lib()
+    L.emu_kv_stats.restype = None
+    L.emu_kv_stats.argtypes = [C.POINTER(C.c_ulonglong)]
+    v = (C.c_ulonglong * 8)()
+    L.emu_kv_stats(v)
+    return dict(zip(KV_STATS, (int(x) for x in v)))
+
+
+def last_windows(n_items: int) -> dict:
+    """w0, w1, kv0, kv1, class and region dwords as build_item_desc stored them for the items of the last liftover_batch call"""
+    L = lib()
+    L.emu_last_windows.restype = C.c_uint32
+    L.emu_last_windows.argtypes = [C.POINTER(C.POINTER(C.c_uint32)), C.c_uint32]
+    arrs = [np.zeros(max(1, n_items), np.uint32) for _ in range(6)]
+    ptrs = (C.POINTER(C.c_uint32) * 6)(*[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrs])
+    n = L.emu_last_windows(ptrs, n_items)
+    assert n == n_items, (n, n_items)
+    return dict(zip(("w0", "w1", "kv0", "kv1", "cls", "region"), (a[:n_items] for a in arrs)))
